@@ -16,11 +16,16 @@ Model "xl" = d_model 1600, 48 layers, 25 heads (d_head 64), d_ff 6400, vocab 100
 Weak scaling: the per-GPU batch is fixed, so global batch = batch * N.
 Timing: W untimed warmup steps, then barrier + synchronize, K steps, synchronize + barrier;
 the slowest rank's wall time is reported (MAX over ranks).
+A plain run does only that: set-up, warmup, the K timed steps, ``--dump-outputs DIR`` (the last timed
+step's loss and a seeded sample of the updated parameters and gradients as ``.npy``), one JSON line.
+``--full`` adds what the headline figure does not need: the clock / power sampler (``gpu_clocks``) and,
+at N > 1, the all-reduce probe, the all-reduce sweep and the DDP-variant sweep.
 """
 
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import socket
@@ -142,6 +147,20 @@ def parse(argv=None):
     ap.add_argument("--clip", type=float, default=0.0, help="global grad-norm clip (0 = off, as the reference bench)")
     ap.add_argument("--backend", default=os.environ.get("CS336_BACKEND", "auto"))
     ap.add_argument("--json-out", default=None)
+    ap.add_argument(
+        "--full",
+        action="store_true",
+        help="also run what the headline figure does not need: the GPU clock / power / temperature sampler over the "
+        "timed steps (gpu_clocks) and, at N > 1, the stand-alone all-reduce probe, the all-reduce sweep "
+        "(--comm-sweep-mb) and the DDP-variant sweep (--ddp-sweep)",
+    )
+    ap.add_argument(
+        "--dump-outputs",
+        default=None,
+        metavar="DIR",
+        help="after the timed steps, write what the last timed step produced as DIR/<name>.npy (float32): loss, and "
+        "a fixed seeded sample of the updated parameters (params) and of their gradients (grads)",
+    )
     ap.add_argument("--no-shadows", action="store_true", help="autocast re-casts weights every forward (A/B)")
     ap.add_argument("--no-fused-layout", action="store_true", help="separate q/k/v and w1/w3 GEMMs (A/B)")
     ap.add_argument(
@@ -174,13 +193,14 @@ def parse(argv=None):
         type=float,
         nargs="*",
         default=[1, 10, 100, 1024],
-        help="N > 1: after the timed steps, fp32 all-reduce sweep (5 warmup + 5 timed each) added to the JSON's dist block",
+        help="N > 1 with --full: after the timed steps, fp32 all-reduce sweep (5 warmup + 5 timed each) added to the "
+        "JSON's dist block",
     )
     ap.add_argument(
         "--ddp-sweep",
         default="auto",
         choices=["auto", "on", "off"],
-        help="N > 1 (auto: with RCCL): after the timed steps, the handout's DDP comparison -- naive / flat / "
+        help="N > 1 with --full (auto: with RCCL): after the timed steps, the handout's DDP comparison -- naive / flat / "
         "per-parameter / bucketed {1,10,100,1000} MB ms/step + comm wait, ZeRO-1 memory -- into the JSON's dist "
         "block (<= 60 s)",
     )
@@ -243,6 +263,36 @@ def self_launch(n: int, argv: list[str]) -> int:
     return subprocess.call(cmd)
 
 
+DUMP_SAMPLE_NUMEL = 6_000_000  # per array: 24 MB of float32, so loss + params + grads stay under 64 MB
+
+
+def dump_outputs(path: str, loss: torch.Tensor, model: torch.nn.Module) -> None:
+    """``--dump-outputs``: what a caller of the timed step holds after the last one -- its loss, the
+    updated parameters and their gradients -- as ``<path>/{loss,params,grads}.npy`` (float32). The
+    parameters (8 GB at XL) and gradients are sampled: from every tensor, in ``named_parameters``
+    order, the same seeded element indices in every run (small tensors whole), concatenated."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    named = list(model.named_parameters())
+    quota = max(1, min(8192, DUMP_SAMPLE_NUMEL // max(len(named), 1)))
+    g = torch.Generator().manual_seed(4321)
+    params, grads = [], []
+    for _, p in named:
+        n = p.numel()
+        idx = None if n <= quota else torch.randint(n, (quota,), generator=g).to(p.device)
+        for t, dst in ((p.detach(), params), (p.grad, grads)):
+            if t is not None:
+                flat = t.reshape(-1)
+                dst.append((flat if idx is None else flat[idx]).float().cpu())
+    arrays = {"loss": loss.detach().float().reshape(1).cpu(), "params": torch.cat(params)}
+    if grads:
+        arrays["grads"] = torch.cat(grads)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
+    log(f"wrote {', '.join(f'{k}.npy ({v.numel()})' for k, v in arrays.items())} to {path}")
+
+
 def comm_sweep(sizes_mb, device, world) -> list[dict]:
     """The reference's all-reduce microbenchmark (``distributed_communication_single.py:28-148``,
     handout p.26: fp32, 5 warmup + timed calls) on the job's own process group, after the timed
@@ -265,11 +315,11 @@ def comm_sweep(sizes_mb, device, world) -> list[dict]:
     return rows
 
 
-def dist_diagnostics(ddp_model, comm_wait_ms, device, world) -> dict:
+def dist_diagnostics(ddp_model, comm_wait_ms, device, world, probe: bool) -> dict:
     """What a multi-GPU run needs to be diagnosable from its own JSON line: exposed communication
     per step (max over ranks), the bucket layout, the process group as the ranks see it, the
-    RCCL version and environment, and a standalone all-reduce of the largest bucket (bus bandwidth
-    without compute beside it)."""
+    RCCL version and environment, and (``probe``: with ``--full``) a standalone all-reduce of the
+    largest bucket (bus bandwidth without compute beside it)."""
     d: dict = {"pg_world_size": dist.get_world_size(), "backend": dist.get_backend()}
     if comm_wait_ms is not None:
         on_dev = dist.get_backend() == "nccl"
@@ -299,7 +349,7 @@ def dist_diagnostics(ddp_model, comm_wait_ms, device, world) -> dict:
     per_rank: list = [None] * dist.get_world_size()
     dist.all_gather_object(per_rank, {"rank": dist.get_rank(), **affinity_info()})
     d["cpu_affinity"] = per_rank
-    if buckets and world > 1 and device.type == "cuda" and dist.get_backend() == "nccl":
+    if probe and buckets and world > 1 and device.type == "cuda" and dist.get_backend() == "nccl":
         n = int(max(mbs) * 2**20 // 4)
         buf = torch.ones(n, dtype=torch.float32, device=device)
         for _ in range(2):
@@ -489,11 +539,14 @@ def main(argv=None):
     barrier()
     sync()
     timing["on"] = True
-    from cs336_systems.utils.gpu_monitor import GpuSampler
+    # --full: clock / power / temperature over the timed window (the JSON's gpu_clocks block): explains
+    # a box-to-box spread of the same tree (DVFS under the MFMA-dense step)
+    if args.full:
+        from cs336_systems.utils.gpu_monitor import GpuSampler
 
-    # clock / power / temperature over the timed window (the JSON's gpu_clocks block): explains a
-    # box-to-box spread of the same tree (DVFS under the MFMA-dense step)
-    sampler = GpuSampler(device)
+        sampler = GpuSampler(device)
+    else:
+        sampler = contextlib.nullcontext()
     ms0 = torch.cuda.memory_stats(device) if device.type == "cuda" else {}
     t_start = time.perf_counter()
     sync_each = os.environ.get("CS336_BENCH_SYNC_EACH", "0") == "1"  # diagnostic: no host run-ahead
@@ -564,8 +617,9 @@ def main(argv=None):
         "model_tflops_per_gpu": round(value * flops_tok / world / 1e12, 1),
         "peak_mem_gib": round(peak_gib, 2),
         "final_loss": round(last_loss, 4),
-        "gpu_clocks": sampler.summary(),
     }
+    if args.full:
+        out["gpu_clocks"] = sampler.summary()
     if device.type == "cuda":  # caching-allocator events inside the timed steps (hipMalloc/hipFree sync)
         out["allocator_timed"] = alloc_timed
     if device.type == "cuda" and not dist_on:
@@ -580,14 +634,16 @@ def main(argv=None):
     gsel = {"blas": "hipblaslt default", "lt": "autotuned hipblaslt (cs336 lt_gemm)",
             "best": "per-problem fastest of hipblaslt default / autotuned lt_gemm / cs336 MFMA GEMM", "hip": "cs336 MFMA GEMM"}[gemm_mode()]
     out["config"]["gemm_selection"] = f"tunableop:{tmode}" if tmode else gsel if device.type == "cuda" else "torch cpu"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model)
     if dist_on:
-        out["dist"] = dist_diagnostics(ddp_model, comm_wait_ms, device, world)
-        if world > 1 and args.comm_sweep_mb:
+        out["dist"] = dist_diagnostics(ddp_model, comm_wait_ms, device, world, probe=args.full)
+        if world > 1 and args.full and args.comm_sweep_mb:
             out["dist"]["allreduce_sweep_fp32"] = comm_sweep(args.comm_sweep_mb, device, world)
     # auto: with RCCL (the driver's multi-GPU runs); a gloo rehearsal stages every all-reduce through
     # the host (minutes per variant at XL), so there it runs only when asked for (--ddp-sweep on)
-    run_sweep = args.ddp_sweep == "on" or (args.ddp_sweep == "auto" and dist.is_initialized()
-                                            and dist.get_backend() == "nccl")
+    run_sweep = args.full and (args.ddp_sweep == "on" or (args.ddp_sweep == "auto" and dist.is_initialized()
+                                                           and dist.get_backend() == "nccl"))
     if world > 1 and run_sweep and not zero:
         # the headline fields are final; free the timed model, then the bounded DDP-variant table
         del ddp_model, opt, model, batches, graphed, eager_step

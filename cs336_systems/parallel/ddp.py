@@ -34,7 +34,7 @@ MI355X/RCCL design notes:
   10 MB, fp32) total ≈ 123 MB, so a 128 MB cap cuts the buckets at layer boundaries (74 buckets of
   61-127 MB, ``profiles/r3_multirank_rehearsal.jsonl``) and the first all-reduce starts after the
   last layer's backward instead of one and a half layers in; (3) the exposed tail of the last bucket
-  stays ≈ 0.75 ms. ``bench.py`` at N > 1 appends an fp32 all-reduce sweep (1/10/100/1024 MB: algbw,
+  stays ≈ 0.75 ms. ``bench.py --full`` at N > 1 appends an fp32 all-reduce sweep (1/10/100/1024 MB: algbw,
   busbw) to its JSON, from which ``w`` and ``o`` of the real node refit ``bucket*``. Measured by
   emulation on one GPU (``scripts/comm_emulation.py``, ``profiles/r5_comm_emulation.md``):
   RCCL-shaped occupants (16 or 32 channel blocks) held for each bucket's W = 8 ring time beside the

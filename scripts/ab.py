@@ -35,7 +35,8 @@ def parse_arm(spec: str) -> tuple[str, dict, list[str]]:
 def command(kind: str, a: argparse.Namespace, extra: list[str], outfile: str) -> list[str]:
     py = sys.executable
     if kind == "bench":
-        return [py, "bench.py", "--steps", str(a.steps), "--warmup", "3", *shlex.split(a.args), *extra]
+        # --full: the gpu_clocks block (clock and power per arm, scripts/ab_summary.py)
+        return [py, "bench.py", "--full", "--steps", str(a.steps), "--warmup", "3", *shlex.split(a.args), *extra]
     if kind == "fa":
         return [py, "scripts/fa_ab.py", *shlex.split(a.args), *extra]
     if kind == "flash":

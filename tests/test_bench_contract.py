@@ -20,7 +20,7 @@ def _run(nproc: int, *extra: str) -> list[dict]:
         "--master-addr", "127.0.0.1", f"--master-port={find_free_port()}",
         "bench.py", "--gpus", str(nproc), "--steps", "2", "--warmup", "1",
         "--model", "tiny", "--ctx", "32", "--batch", "2", "--dtype", "fp32", "--comm-sweep-mb", "1", "4",
-        "--ddp-sweep", "on", *extra,
+        "--ddp-sweep", "on", "--full", *extra,
     ]
     env = dict(os.environ, CS336_DIST_BACKEND="gloo", OMP_NUM_THREADS="1")
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=300)
@@ -94,6 +94,52 @@ def test_bench_ddp_sweep_watchdog():
     d = lines[0]
     assert d["n_gpus"] == 2 and d["value"] > 0
     assert "error" in d["dist"]["ddp_sweep"] and "ddp_variants" not in d["dist"]
+
+
+def _run_plain(*extra: str) -> dict:
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--model", "tiny", "--ctx", "32",
+           "--batch", "2", "--dtype", "fp32", *extra]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env.update(OMP_NUM_THREADS="1")
+    out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [json.loads(line) for line in out.stdout.splitlines() if line.startswith("{")]
+    assert len(lines) == 1, lines
+    return lines[0]
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without ``--full`` the result line carries the headline fields and none of the extra measurements;
+    ``--dump-outputs`` writes the last step's loss and the sampled parameters / gradients as float32
+    ``.npy`` files, from the same inputs and the same sample in every run."""
+    import numpy as np
+
+    runs = []
+    for name in ("a", "b"):
+        d = _run_plain("--dump-outputs", str(tmp_path / name))
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d
+        assert d["steps"] == 2 and d["n_gpus"] == 1 and d["ms_per_step"] > 0
+        assert d["value"] == pytest.approx(2 * 32 / (d["ms_per_step"] / 1e3), rel=0.02)
+        assert "gpu_clocks" not in d and "dist" not in d
+        files = sorted(p.name for p in (tmp_path / name).iterdir())
+        assert files == ["grads.npy", "loss.npy", "params.npy"]
+        arrays = {f[:-4]: np.load(tmp_path / name / f, allow_pickle=False) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 * 2**20
+        assert arrays["loss"].shape == (1,) and arrays["loss"][0] == pytest.approx(d["final_loss"], abs=1e-4)
+        assert arrays["params"].shape == arrays["grads"].shape
+        runs.append(arrays)
+    for f in runs[0]:  # same inputs, same sample: the two runs agree (to rounding where a GPU kernel adds atomically)
+        np.testing.assert_allclose(runs[0][f], runs[1][f], rtol=1e-4, atol=1e-5, err_msg=f)
+    assert np.abs(runs[0]["grads"]).max() > 0
+
+
+def test_bench_full_adds_gpu_clocks():
+    d = _run_plain("--full")
+    assert "samples" in d["gpu_clocks"]
+    if not _gpu_visible():
+        assert d["gpu_clocks"]["error"] == "not a GPU run"
 
 
 def test_bench_self_launch_without_launcher():
