@@ -1,4 +1,5 @@
 from .configs import DEFAULT_THETA, DEFAULT_VOCAB, MODEL_CONFIGS, get_model_config, param_count, train_flops_per_token
+from .kv_cache import KVCache
 from .transformer import (
     BasicsTransformerLM,
     CausalMultiHeadSelfAttention,
@@ -28,6 +29,7 @@ __all__ = [
     "BasicsTransformerLM",
     "CausalMultiHeadSelfAttention",
     "Embedding",
+    "KVCache",
     "Linear",
     "RMSNorm",
     "RotaryEmbedding",

@@ -1,0 +1,61 @@
+"""Key / value cache of ``BasicsTransformerLM.forward_cached``.
+
+``k`` and ``v`` are ``(L, B, H, max_len, d)``: ``cache.k[l]`` is the ``(B, H, max_len, d)`` view the
+decode-attention kernel reads in place (layer and batch are the outer dims, so a layer slice or a
+batch sub-view needs no copy). K rows are stored rotated (RoPE at the row's position). ``lengths``
+is the per-sequence int32 length on the device (what the kernels read); ``length`` is its host
+mirror: ``generate`` batches are rectangular, so one number describes them all and no step has to
+read the device tensor back."""
+
+from __future__ import annotations
+
+import torch
+
+
+class KVCache:
+    def __init__(self, model_or_dims, batch: int, max_len: int | None = None, device=None, dtype=None):
+        """``model_or_dims``: a ``BasicsTransformerLM`` (layers, heads, head dim, ``context_length``,
+        device and parameter dtype are taken from it) or ``(num_layers, num_heads, d_head)``."""
+        if isinstance(model_or_dims, (tuple, list)):
+            L, H, d = (int(x) for x in model_or_dims)
+            if max_len is None:
+                raise ValueError("KVCache from dims needs max_len")
+        else:
+            m = model_or_dims
+            attn = m.layers[0].attn
+            L, H, d = len(m.layers), attn.num_heads, attn.d_k
+            w = attn.q_proj.weight
+            if max_len is None:
+                max_len = m.context_length
+            if device is None:
+                device = w.device
+            if dtype is None:
+                dtype = w.dtype
+        if batch < 1 or max_len < 1:
+            raise ValueError("KVCache needs batch >= 1 and max_len >= 1")
+        self.num_layers, self.batch, self.num_heads, self.max_len, self.d_head = L, int(batch), H, int(max_len), d
+        self.k = torch.zeros(L, batch, H, max_len, d, device=device, dtype=dtype)
+        self.v = torch.zeros_like(self.k)
+        self.lengths = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.length = 0
+
+    @property
+    def device(self):
+        return self.k.device
+
+    @property
+    def dtype(self):
+        return self.k.dtype
+
+    def reset(self) -> None:
+        """Forget every cached token (the rows are not cleared: rows beyond ``length`` are never read)."""
+        self.lengths.zero_()
+        self.length = 0
+
+    def advance(self, n: int) -> None:
+        self.lengths += n
+        self.length += n
+
+    def __repr__(self):
+        return (f"KVCache(layers={self.num_layers}, batch={self.batch}, heads={self.num_heads}, "
+                f"max_len={self.max_len}, d_head={self.d_head}, length={self.length}, dtype={self.k.dtype})")

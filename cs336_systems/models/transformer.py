@@ -371,6 +371,49 @@ class CausalMultiHeadSelfAttention(nn.Module):
         with annotate("out_proj"):
             return self.output_proj(o)
 
+    def forward_cached(self, x3, k_cache, v_cache, start: int, pos=None, kv_len=None) -> torch.Tensor:
+        """Attention of ``forward_cached`` (inference only). ``x3`` (B, n, d_model); ``k_cache`` /
+        ``v_cache`` this layer's (B, H, max_len, dk) cache views. ``start == 0``: prefill -- the
+        ordinary causal attention over the n tokens at positions 0..n-1, whose rotated K and V are
+        copied into cache rows [0, n). Otherwise one decode step (n == 1): ``pos`` (B,) int32 is the
+        new token's slot and RoPE position, ``kv_len = pos + 1`` its key count."""
+        B, n, _ = x3.shape
+        H, dk = self.num_heads, self.d_k
+        w = [self.q_proj.weight, self.k_proj.weight, self.v_proj.weight]
+        with annotate("qkv_proj"):
+            if x3.is_cuda and fused.grouped_view(w) is not None:
+                qkv = fused.fused_linear(x3, *w)  # one grouped QKV GEMM, (B, n, 3*H*dk)
+            else:
+                qkv = torch.cat([self.q_proj(x3), self.k_proj(x3), self.v_proj(x3)], dim=-1)
+        if qkv.dtype != k_cache.dtype:
+            raise ValueError(f"KV cache dtype {k_cache.dtype} does not match the compute dtype {qkv.dtype}")
+        if start > 0:
+            with annotate("kv_append_rope"):
+                q = ops.kv_append_rope(qkv.view(B, 3 * H * dk), self.positional_encoder.cos, self.positional_encoder.sin,
+                                       pos, k_cache, v_cache)
+            with annotate("decode_attention"):
+                o, _ = ops.decode_attention(q, k_cache, v_cache, kv_len, max_kv_len=start + 1)
+            o = o.reshape(B, 1, H * dk)
+        else:
+            q, k, v = (qkv.view(B, n, 3, H, dk)[:, :, i].transpose(1, 2) for i in range(3))
+            with annotate("rope"):
+                q = self.positional_encoder(q, None)
+                k = self.positional_encoder(k, None)
+            k_cache[:, :, :n].copy_(k)
+            v_cache[:, :, :n].copy_(v)
+            impl = _ATTN_IMPL
+            with annotate("attention"):
+                if impl == "naive" or (impl == "auto" and not x3.is_cuda):
+                    seq = torch.arange(n, device=x3.device)
+                    o = scaled_dot_product_attention(q, k, v, seq[:, None] >= seq[None, :])
+                elif x3.is_cuda:
+                    o = ops.flash_attention(q, k.to(q.dtype), v.to(q.dtype), is_causal=True)
+                else:
+                    o = ops.FlashAttentionTorch.apply(q, k, v, True)
+            o = o.transpose(1, 2).reshape(B, n, H * dk)
+        with annotate("out_proj"):
+            return self.output_proj(o)
+
 
 class TransformerBlock(nn.Module):
     """Pre-norm block: ``x + attn(ln1(x))`` then ``+ ffn(ln2(.))`` (``model.py:330-386``)."""
@@ -554,6 +597,61 @@ class BasicsTransformerLM(nn.Module):
             return self.lm_head(y)
 
     @torch.no_grad()
+    def forward_cached(self, x: torch.Tensor, cache) -> torch.Tensor:
+        """Logits ``(B, n, vocab)`` of the ``n`` tokens ``x`` that follow the ``cache.length`` tokens
+        already in ``cache`` (a :class:`~cs336_systems.models.kv_cache.KVCache`); the cache then
+        holds them too. On an empty cache this is the prefill (any ``n >= 1``: the ordinary forward,
+        with every layer's rotated K and V copied into the cache); afterwards one token per call
+        (``n == 1``): per layer the QKV projection of that token alone, ``ops.kv_append_rope`` and
+        ``ops.decode_attention`` over the cached keys -- O(1) projection and O(length) attention work
+        per token instead of a forward over the whole window."""
+        if getattr(self, "tensor_parallel", None) is not None or any(
+                layer.attn.context_parallel is not None for layer in self.layers):
+            raise NotImplementedError("forward_cached does not support tensor / context parallelism")
+        if x.dim() != 2:
+            raise ValueError("forward_cached takes (B, n) token ids")
+        B, n = x.shape
+        if B != cache.batch:
+            raise ValueError(f"batch {B} does not match the cache's {cache.batch}")
+        if cache.num_layers != len(self.layers):
+            raise ValueError("cache was built for a different number of layers")
+        start = cache.length
+        if n < 1:
+            raise ValueError("forward_cached needs at least one token")
+        if start > 0 and n > 1:
+            raise NotImplementedError("chunked prefill (n > 1 on a non-empty cache) is not supported")
+        if start + n > min(cache.max_len, self.context_length):
+            raise ValueError(f"{start} cached + {n} new tokens exceed the cache (max_len {cache.max_len}, "
+                             f"context_length {self.context_length})")
+        pos = kv_len = None
+        if start > 0:  # once per step, shared by all layers
+            pos = cache.lengths
+            kv_len = cache.lengths + 1
+        with annotate("embed"):
+            h = self.token_embeddings(x)
+        n_layers = len(self.layers)
+        if n_layers and self._fused_residual_ok(h):
+            y = self.layers[0].ln1(h)
+            for i, layer in enumerate(self.layers):
+                with annotate(f"layer{i}"):
+                    a = layer.attn.forward_cached(y, cache.k[i], cache.v[i], start, pos, kv_len)
+                    self._reading(layer.ln2)
+                    h, y = ops.add_rmsnorm(h, a, layer.ln2.weight, layer.ln2.eps)
+                    f = layer.ffn(y)
+                    nxt = self.layers[i + 1].ln1 if i + 1 < n_layers else self.ln_final
+                    self._reading(nxt)
+                    h, y = ops.add_rmsnorm(h, f, nxt.weight, nxt.eps)
+        else:
+            for i, layer in enumerate(self.layers):
+                with annotate(f"layer{i}"):
+                    h = h + layer.attn.forward_cached(layer.ln1(h), cache.k[i], cache.v[i], start, pos, kv_len)
+                    h = h + layer.ffn(layer.ln2(h))
+            y = self.ln_final(h)
+        cache.advance(n)
+        with annotate("lm_head"):
+            return self.lm_head(y)
+
+    @torch.no_grad()
     def generate(
         self,
         x: torch.Tensor,
@@ -561,15 +659,36 @@ class BasicsTransformerLM(nn.Module):
         temperature: float = 1.0,
         top_k: int | None = None,
         eos_token_id: int | None = None,
+        use_cache: bool = False,
     ) -> torch.Tensor:
         """Autoregressive sampling (``model.py:255-310``) with a working top-k filter (the
-        reference's ``masked_fill`` is not in place and its threshold broadcast is wrong for B>1)."""
+        reference's ``masked_fill`` is not in place and its threshold broadcast is wrong for B>1).
+
+        ``use_cache=True``: prefill a KV cache on the prompt (its last ``context_length`` tokens),
+        then one :meth:`forward_cached` step per token while the sequence fits the window; once the
+        window is full the remaining tokens take the uncached sliding-window step (a window that
+        slides re-positions every key, which only a full recomputation defines)."""
         if x.dim() == 1:
             x = x.unsqueeze(0)
         orig = x.size(-1)
+        cache = None
+        if use_cache and max_new_tokens > 0:
+            from .kv_cache import KVCache
+
+            w = self.lm_head.weight
+            dev = w.device.type
+            cdt = torch.get_autocast_dtype(dev) if torch.is_autocast_enabled(dev) else w.dtype
+            cache = KVCache(self, x.size(0), device=w.device, dtype=cdt)
         for _ in range(max_new_tokens):
             ctx = x[:, -self.context_length :] if x.size(1) > self.context_length else x
-            logits = self.forward(ctx)[:, -1].float() / temperature
+            if cache is not None and cache.length == 0:
+                logits = self.forward_cached(ctx, cache)  # prefill
+            elif cache is not None and cache.length + 1 == x.size(1) <= self.context_length:
+                logits = self.forward_cached(x[:, -1:], cache)
+            else:
+                cache = None  # the window is full (and slides from here on): full recomputation
+                logits = self.forward(ctx)
+            logits = logits[:, -1].float() / temperature
             if top_k:
                 vals, _ = torch.topk(logits, min(top_k, logits.size(-1)))
                 logits = logits.masked_fill(logits < vals[:, -1:], float("-inf"))

@@ -157,3 +157,16 @@ def _swiglu_fused_bwd(dh, y):
 @register_fake("cs336::multi_tensor_cast_bf16")
 def _cast_bf16(src, dst):
     return None
+
+
+if hasattr(torch.ops.cs336, "fa_decode"):  # (absent from libraries built before the KV cache: A/B baselines)
+
+    @register_fake("cs336::fa_decode")
+    def _fa_decode(q, k_cache, v_cache, kv_len, scale, max_kv_len, splits=0):
+        B, H, D = q.shape
+        return q.new_empty((B, H, D)), q.new_empty((B, H), dtype=torch.float32)
+
+    @register_fake("cs336::kv_append_rope")
+    def _kv_append_rope(qkv, cos, sin, pos, k_cache, v_cache):
+        B, H, _, D = k_cache.shape
+        return qkv.new_empty((B, H, D))

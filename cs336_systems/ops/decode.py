@@ -1,0 +1,96 @@
+"""Single-token attention against a KV cache and the append of the new token's K / V row, eager
+references + HIP kernels (``csrc/flash_attn/fa_decode.hip``).
+
+``decode_attention``: one query row per (batch, head), ``q`` (B, H, d), against keys
+``[0, kv_len[b])`` of ``(B, H, max_len, d)`` cache views (any batch / head strides: a layer slice of
+a larger cache tensor is passed as is). ``kv_len`` is an int32 device tensor; nothing synchronizes
+the host. Returns ``o`` (B, H, d) in q's dtype and the natural-log ``lse`` (B, H) fp32. A sequence
+with ``kv_len == 0`` gives ``o = 0`` and ``lse = -inf``. Rows at and beyond ``kv_len[b]`` are never
+used and may hold anything.
+
+``kv_append_rope``: the new token's fused projection row ``qkv`` (B, 3*H*d; q|k|v) -> rotated q
+(B, H, d); rotated k and plain v are written into row ``pos[b]`` of every (b, h) cache plane. A
+``pos[b]`` outside the cache stores nothing.
+
+The HIP kernels take head dims 32 / 64 / 80 / 128 (the ones the model's fused attention path takes);
+other head dims run the reference. On a GPU with the HIP backend a missing extension raises.
+"""
+
+from __future__ import annotations
+
+import math
+
+import torch
+
+from ._ext import ops, use_hip
+from .rope import rope_ref
+
+_DECODE_D = (32, 64, 80, 128)
+
+
+def decode_attention_ref(q, k_cache, v_cache, kv_len, scale=None):
+    """Masked softmax over the first ``kv_len[b]`` keys, fp32 (or fp64) math. Cache rows beyond the
+    valid range are replaced before any arithmetic, so NaNs there cannot leak."""
+    B, H, d = q.shape
+    scale = 1.0 / math.sqrt(d) if scale is None else scale
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    n = k_cache.shape[2]
+    valid = torch.arange(n, device=q.device)[None, :] < kv_len.to(torch.int64)[:, None]  # (B, n)
+    vm = valid[:, None, :, None]
+    k = torch.where(vm, k_cache.to(ct), 0.0)
+    v = torch.where(vm, v_cache.to(ct), 0.0)
+    s = torch.einsum("bhd,bhnd->bhn", q.to(ct), k) * scale
+    s = torch.where(valid[:, None, :], s, float("-inf"))
+    lse = torch.logsumexp(s, dim=-1)
+    p = torch.exp(s - torch.where(torch.isinf(lse), 0.0, lse)[..., None])  # empty row: exp(-inf) = 0
+    o = torch.einsum("bhn,bhnd->bhd", p, v)
+    return o.to(q.dtype), lse.float()
+
+
+def kv_append_rope_ref(qkv, cos, sin, pos, k_cache, v_cache):
+    B, H, max_len, d = k_cache.shape
+    q, k, v = qkv.reshape(B, 3, H, d).unbind(1)
+    ok = (pos >= 0) & (pos < min(max_len, cos.shape[0]))
+    p = pos.to(torch.int64).clamp(0, min(max_len, cos.shape[0]) - 1)
+    # rope_ref rotates (..., seq, d) at positions broadcastable to x[..., 0]: (B, H, 1, d) at (B, 1, 1)
+    q_rot = rope_ref(q.unsqueeze(2), cos, sin, p[:, None, None]).squeeze(2)
+    k_rot = rope_ref(k.unsqueeze(2), cos, sin, p[:, None, None]).squeeze(2)
+    idx = p[:, None, None, None].expand(B, H, 1, d)
+    keep = ok[:, None, None, None]
+    k_cache.scatter_(2, idx, torch.where(keep, k_rot.unsqueeze(2).to(k_cache.dtype), k_cache.gather(2, idx)))
+    v_cache.scatter_(2, idx, torch.where(keep, v.unsqueeze(2).to(v_cache.dtype), v_cache.gather(2, idx)))
+    return torch.where(ok[:, None, None], q_rot, torch.zeros_like(q_rot)).contiguous()
+
+
+def _cache_layout_ok(t: torch.Tensor) -> bool:
+    es = t.element_size()
+    return (t.dim() == 4 and t.stride(-1) == 1 and t.data_ptr() % 16 == 0
+            and all((t.stride(i) * es) % 16 == 0 for i in range(3)))
+
+
+def decode_attention(q, k_cache, v_cache, kv_len, scale=None, max_kv_len=None, splits=0):
+    """``max_kv_len``: host-known upper bound of ``kv_len`` (default: the cache's ``max_len``), used
+    only to choose the split count; ``splits``: 0 = choose, n = exactly n key splits."""
+    d = q.shape[-1]
+    scale = 1.0 / math.sqrt(d) if scale is None else float(scale)
+    if (use_hip(q, k_cache, v_cache) and d in _DECODE_D and q.dtype in (torch.bfloat16, torch.float16, torch.float32)
+            and _cache_layout_ok(k_cache) and _cache_layout_ok(v_cache)):
+        max_len = k_cache.shape[2]
+        bound = max_len if max_kv_len is None else min(int(max_kv_len), max_len)
+        if kv_len.dtype != torch.int32:
+            kv_len = kv_len.to(torch.int32)
+        return ops().fa_decode(q, k_cache, v_cache, kv_len.contiguous(), scale, bound, int(splits))
+    return decode_attention_ref(q, k_cache, v_cache, kv_len, scale)
+
+
+def kv_append_rope(qkv, cos, sin, pos, k_cache, v_cache):
+    d = k_cache.shape[-1]
+    if (use_hip(qkv, k_cache, v_cache) and d % 8 == 0 and 8 <= d <= 256
+            and qkv.dtype in (torch.bfloat16, torch.float16, torch.float32) and qkv.dim() == 2 and qkv.stride(-1) == 1
+            and qkv.data_ptr() % 16 == 0 and (qkv.stride(0) * qkv.element_size()) % 16 == 0
+            and _cache_layout_ok(k_cache) and _cache_layout_ok(v_cache)):
+        if pos.dtype != torch.int32:
+            pos = pos.to(torch.int32)
+        return ops().kv_append_rope(qkv, cos.float().contiguous(), sin.float().contiguous(), pos.contiguous(),
+                                    k_cache, v_cache)
+    return kv_append_rope_ref(qkv, cos, sin, pos, k_cache, v_cache)

@@ -1340,7 +1340,132 @@ void splitk_sum(const at::Tensor& slabs, at::Tensor& out, bool accumulate) {
                              accumulate, stream());
 }
 
+// ------------------------------------------------------------------------------------------
+// Decode attention over a KV cache / append of the new token (csrc/flash_attn/fa_decode.hip)
+// ------------------------------------------------------------------------------------------
+// (B, H, max_len, D) cache view: contiguous last dim, 16-B aligned base and rows, any batch / head
+// strides (a layer slice or a batch sub-view of a larger cache tensor needs no copy)
+void check_cache(const at::Tensor& t, const char* name) {
+  check_cuda(t, name);
+  TORCH_CHECK(t.dim() == 4, "cs336: ", name, " must be (B, H, max_len, D)");
+  TORCH_CHECK(t.stride(3) == 1, "cs336: ", name, " must have a contiguous last dim");
+  const int64_t es = t.element_size();
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(t.data_ptr()) % 16) == 0, "cs336: ", name, " must be 16-byte aligned");
+  TORCH_CHECK((t.stride(2) * es) % 16 == 0 && (t.stride(1) * es) % 16 == 0 && (t.stride(0) * es) % 16 == 0,
+              "cs336: ", name, " strides must be multiples of 16 bytes");
+  TORCH_CHECK(t.stride(0) >= 0 && t.stride(1) >= 0 && t.stride(2) >= t.size(3), "cs336: ", name,
+              " rows must not overlap");
+  TORCH_CHECK(t.size(2) < ((int64_t)1 << 31), "cs336: ", name, " max_len must fit 32 bits");
+}
+
+std::tuple<at::Tensor, at::Tensor> fa_decode(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                                             const at::Tensor& kv_len, double scale, int64_t max_kv_len,
+                                             int64_t splits) {
+  check_cuda(q, "q");
+  check_cache(k_cache, "k_cache");
+  check_cache(v_cache, "v_cache");
+  TORCH_CHECK(q.dim() == 3, "cs336: fa_decode q must be (B, H, D)");
+  const int64_t B = q.size(0), H = q.size(1), D = q.size(2), max_len = k_cache.size(2);
+  TORCH_CHECK(D == 32 || D == 64 || D == 80 || D == 128, "cs336: fa_decode head dim must be 32, 64, 80 or 128 (got ", D,
+              ")");
+  TORCH_CHECK(q.scalar_type() == k_cache.scalar_type() && q.scalar_type() == v_cache.scalar_type(),
+              "cs336: q / k_cache / v_cache dtype mismatch");
+  TORCH_CHECK(k_cache.sizes() == v_cache.sizes() && k_cache.size(0) == B && k_cache.size(1) == H &&
+                  k_cache.size(3) == D,
+              "cs336: caches must be (B, H, max_len, D) matching q");
+  TORCH_CHECK(k_cache.device() == q.device() && v_cache.device() == q.device() && kv_len.device() == q.device(),
+              "cs336: fa_decode tensors must be on one device");
+  TORCH_CHECK(kv_len.scalar_type() == at::kInt && kv_len.dim() == 1 && kv_len.size(0) == B && kv_len.is_contiguous(),
+              "cs336: kv_len must be a contiguous int32 (B,) device tensor");
+  TORCH_CHECK(max_kv_len >= 0 && max_kv_len <= max_len, "cs336: max_kv_len must be in [0, max_len]");
+  TORCH_CHECK(splits >= 0 && splits <= 64, "cs336: splits must be in [0, 64] (0 = choose)");
+  TORCH_CHECK(B * H * 64 < ((int64_t)1 << 31), "cs336: fa_decode grid too large");
+  const DType t = to_dtype(q);
+  c10::DeviceGuard g(q.device());
+  const at::Tensor qc = q.contiguous();
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(qc.data_ptr()) % 16) == 0, "cs336: q must be 16-byte aligned");
+  at::Tensor o = at::empty({B, H, D}, q.options());
+  at::Tensor lse = at::empty({B, H}, q.options().dtype(at::kFloat));
+  if (B * H == 0) return {o, lse};
+  cs336::DecodeParams p;
+  p.q = qc.data_ptr();
+  p.k = k_cache.data_ptr();
+  p.v = v_cache.data_ptr();
+  p.o = o.data_ptr();
+  p.lse = lse.data_ptr<float>();
+  p.kv_len = kv_len.data_ptr<int>();
+  p.k_sb = k_cache.stride(0); p.k_sh = k_cache.stride(1); p.k_sn = k_cache.stride(2);
+  p.v_sb = v_cache.stride(0); p.v_sh = v_cache.stride(1); p.v_sn = v_cache.stride(2);
+  p.B = (int)B; p.H = (int)H; p.D = (int)D; p.max_len = (int)max_len;
+  p.scale = (float)scale;
+  p.splits = splits > 0 ? (int)splits : cs336::fa_decode_splits((int)B, (int)H, (int)D, t, (int)max_kv_len);
+  at::Tensor ws;
+  if (p.splits > 1) {
+    ws = at::empty({(int64_t)p.splits * B * H * (D + 1)}, q.options().dtype(at::kFloat));
+    p.opart = ws.data_ptr<float>();
+    p.lpart = p.opart + (int64_t)p.splits * B * H * D;
+  }
+  cs336::fa_decode(p, t, stream());
+  return {o, lse};
+}
+
+// the split count fa_decode(..., splits=0) picks (benchmarks and profiles report it)
+int64_t fa_decode_splits(int64_t B, int64_t H, int64_t D, int64_t elem_size, int64_t max_kv_len) {
+  return cs336::fa_decode_splits((int)B, (int)H, (int)D, elem_size == 4 ? DType::F32 : DType::BF16, (int)max_kv_len);
+}
+
+at::Tensor kv_append_rope(const at::Tensor& qkv, const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& pos,
+                          at::Tensor& k_cache, at::Tensor& v_cache) {
+  check_cuda(qkv, "qkv");
+  check_cache(k_cache, "k_cache");
+  check_cache(v_cache, "v_cache");
+  TORCH_CHECK(qkv.dim() == 2 && qkv.stride(1) == 1, "cs336: qkv must be (B, 3*H*D) with a contiguous last dim");
+  const int64_t B = k_cache.size(0), H = k_cache.size(1), max_len = k_cache.size(2), D = k_cache.size(3);
+  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "cs336: k_cache / v_cache shape mismatch");
+  TORCH_CHECK(qkv.size(0) == B && qkv.size(1) == 3 * H * D, "cs336: qkv must be (B, 3*H*D) for (B, H, max_len, D) caches");
+  TORCH_CHECK(D >= 8 && D <= 256 && D % 8 == 0, "cs336: kv_append_rope head dim must be a multiple of 8 in [8, 256]");
+  TORCH_CHECK(qkv.scalar_type() == k_cache.scalar_type() && qkv.scalar_type() == v_cache.scalar_type(),
+              "cs336: qkv / k_cache / v_cache dtype mismatch");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16) == 0 && (qkv.stride(0) * qkv.element_size()) % 16 == 0 &&
+                  qkv.stride(0) >= 0,
+              "cs336: qkv rows must be 16-byte aligned");
+  TORCH_CHECK(cos.is_cuda() && sin.is_cuda() && cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat &&
+                  cos.dim() == 2 && cos.is_contiguous() && sin.is_contiguous() && cos.sizes() == sin.sizes() &&
+                  cos.size(1) * 2 == D,
+              "cs336: rope cache must be contiguous fp32 (ctx, D/2)");
+  TORCH_CHECK(pos.scalar_type() == at::kInt && pos.dim() == 1 && pos.size(0) == B && pos.is_contiguous(),
+              "cs336: pos must be a contiguous int32 (B,) device tensor");
+  TORCH_CHECK(pos.device() == qkv.device() && cos.device() == qkv.device() && sin.device() == qkv.device() &&
+                  k_cache.device() == qkv.device() && v_cache.device() == qkv.device(),
+              "cs336: kv_append_rope tensors must be on one device");
+  TORCH_CHECK(B * 3 * H * (D / 8) < ((int64_t)1 << 31) && cos.size(0) < ((int64_t)1 << 31),
+              "cs336: kv_append_rope too large for 32-bit indexing");
+  c10::DeviceGuard g(qkv.device());
+  at::Tensor q_out = at::empty({B, H, D}, qkv.options());
+  if (B * H == 0) return q_out;
+  cs336::AppendParams p;
+  p.qkv = qkv.data_ptr();
+  p.qkv_sb = qkv.stride(0);
+  p.cos = cos.data_ptr<float>();
+  p.sin = sin.data_ptr<float>();
+  p.pos = pos.data_ptr<int>();
+  p.q_out = q_out.data_ptr();
+  p.k = k_cache.data_ptr();
+  p.v = v_cache.data_ptr();
+  p.k_sb = k_cache.stride(0); p.k_sh = k_cache.stride(1); p.k_sn = k_cache.stride(2);
+  p.v_sb = v_cache.stride(0); p.v_sh = v_cache.stride(1); p.v_sn = v_cache.stride(2);
+  p.B = (int)B; p.H = (int)H; p.D = (int)D; p.max_len = (int)max_len; p.ctx = (int)cos.size(0);
+  cs336::kv_append_rope(p, to_dtype(qkv), stream());
+  return q_out;
+}
+
 TORCH_LIBRARY(cs336, m) {
+  m.def(
+      "fa_decode(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_len, float scale, int max_kv_len, int splits=0) "
+      "-> (Tensor o, Tensor lse)");
+  m.def("fa_decode_splits(int B, int H, int D, int elem_size, int max_kv_len) -> int", &fa_decode_splits);
+  m.def(
+      "kv_append_rope(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor(a!) k_cache, Tensor(b!) v_cache) -> Tensor");
   m.def(
       "fa_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale, Tensor? rope_cos=None, Tensor? rope_sin=None, "
       "Tensor? rope_pos=None) -> (Tensor, Tensor)");
@@ -1402,6 +1527,8 @@ TORCH_LIBRARY(cs336, m) {
 }
 
 TORCH_LIBRARY_IMPL(cs336, CUDA, m) {
+  m.impl("fa_decode", &fa_decode);
+  m.impl("kv_append_rope", &kv_append_rope);
   m.impl("fa_fwd", &fa_fwd);
   m.impl("fa_fwd_ot", &fa_fwd_ot);
   m.impl("fa_bwd", &fa_bwd);

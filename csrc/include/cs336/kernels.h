@@ -221,4 +221,45 @@ size_t flash_attn_bwd_hs_workspace(const AttnBwdParams& p);
 // rope_dq = false (with RoPE): only dK is rotated back in the kernel; the caller rotates dQ
 void flash_attn_bwd_hs(const AttnBwdParams& p, DType t, float* ws, hipStream_t s, bool rope_dq = true);
 
+// ---- decode attention over a KV cache (csrc/flash_attn/fa_decode.hip) ----
+// One query row per (batch, head) against keys [0, kv_len[b]) of the cache; D in {32, 64, 80, 128}.
+struct DecodeParams {
+  const void* q;  // (B, H, D) contiguous
+  const void* k;  // (B, H, max_len, D) views: element strides below, last dim contiguous, 16-B rows
+  const void* v;
+  void* o;             // (B, H, D) contiguous, q's dtype
+  float* lse;          // (B, H) natural-log LSE
+  const int* kv_len;   // (B,) device; clamped to [0, max_len] in the kernel
+  int64_t k_sb, k_sh, k_sn;
+  int64_t v_sb, v_sh, v_sn;
+  int B, H, D, max_len;
+  float scale;
+  // splits > 1: fp32 partials opart (splits, B*H, D) / lpart (splits, B*H), merged by a second launch
+  int splits = 1;
+  float* opart = nullptr;
+  float* lpart = nullptr;
+};
+int fa_decode_key_tile(int D, DType t);
+// split count the host picks from the upper bound max_kv_len (1 = single launch, no workspace)
+int fa_decode_splits(int B, int H, int D, DType t, int max_kv_len);
+void fa_decode(const DecodeParams& p, DType t, hipStream_t s);
+
+// New token's fused projection row qkv (B, 3*H*D; q|k|v): rotated q -> q_out (B, H, D), rotated k and
+// plain v -> row pos[b] of the cache planes. pos[b] outside [0, min(max_len, ctx)) stores nothing to
+// the cache (q_out row zeroed). D % 8 == 0.
+struct AppendParams {
+  const void* qkv;
+  int64_t qkv_sb;  // row stride (elements)
+  const float* cos;  // (ctx, D/2) fp32
+  const float* sin;
+  const int* pos;  // (B,) device
+  void* q_out;
+  void* k;
+  void* v;
+  int64_t k_sb, k_sh, k_sn;
+  int64_t v_sb, v_sh, v_sn;
+  int B, H, D, max_len, ctx;
+};
+void kv_append_rope(const AppendParams& p, DType t, hipStream_t s);
+
 }  // namespace cs336

@@ -1,0 +1,42 @@
+"""Register-spill guard for the decode-attention and KV-append kernels (CPU: hipcc cross-compiles
+gfx950 here), by the recipe of ``test_kernel_resources.py``: the memory-bound decode loop keeps its
+K / V rows, the query slice and the output slice in registers, and a spill to scratch would put
+extra memory traffic into exactly the path that is limited by it. Every kernel of the file must
+compile with ScratchSize 0 under the build's own flags; there is no exceptions list."""
+
+import os
+import re
+import subprocess
+
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = "/opt/rocm/bin/hipcc"
+SOURCES = ["csrc/flash_attn/fa_decode.hip"]  # (the append kernel lives in the same file)
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@pytest.mark.parametrize("src", SOURCES)
+def test_no_scratch(src, tmp_path):
+    from cs336_systems._native import build
+
+    path = os.path.join(REPO, src)
+    head = open(path).read(4096)
+    flags = ["-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(REPO, "csrc", "include"),
+             "-I" + os.path.join(REPO, "csrc", "flash_attn"), "--offload-arch=gfx950", "-munsafe-fp-atomics"]
+    if "cs336-build: agpr-accumulators" not in head:
+        flags += list(build.VGPR_FORM)
+    if "cs336-build: no-slp" in head:
+        flags += ["-fno-slp-vectorize"]
+    r = subprocess.run([HIPCC, *flags, "-Rpass-analysis=kernel-resource-usage", "-c", path, "-o",
+                        str(tmp_path / "k.o")], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    names = re.findall(r"Function Name: (\S+)", r.stderr)
+    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
+    assert names and len(names) == len(scratch)
+    # 3 dtypes x 4 head dims of the decode and merge kernels, 3 dtypes of the append kernel
+    assert sum("fa_decode_kernel" in n for n in names) == 12
+    assert sum("fa_decode_merge_kernel" in n for n in names) == 12
+    assert sum("kv_append_rope_kernel" in n for n in names) == 3
+    spills = [(n, s) for n, s in zip(names, scratch) if s]
+    assert not spills, spills
