@@ -5,6 +5,8 @@ HIP path (``csrc/ops/xent.hip``): one workgroup per row computes an online max/s
 vocab in a single read of the (bf16 or fp32) logits, writes the per-row loss and LSE; the
 backward writes ``(softmax - onehot) * g / M`` in the logits dtype in one pass. The upstream
 gradient ``g`` is read from device memory, so there is no host sync anywhere in the loss.
+Masked logits (``-inf``) are allowed as long as a row keeps one finite entry: they add nothing to
+the sum and get a gradient of exactly 0.
 """
 
 from __future__ import annotations

@@ -6,14 +6,21 @@
 // strided slice of the vocab (one read of the logits, 8 B per lane per access), then a
 // wave-shuffle + LDS merge of the (m, s) pairs. Backward: dz = (exp(z - lse) - onehot(t)) * g * mult,
 // with the upstream scalar g read from device memory (no host sync), written in the logits dtype.
+//
+// Masked logits (-inf): the running max starts at the finite sentinel -FLT_MAX, not -inf, so the
+// lane loops never form exp(-inf - (-inf)) = NaN when the first values a lane sees are -inf; a -inf
+// logit adds exp(-inf) = 0 at no extra compare, and a lane that owns nothing merges as (sentinel, 0).
+// The row loss is log S - (z[t] - M): M + log S rounds to an ulp of |M| (1e-3 at |z| ~ 1e4), which
+// the difference with z[t] would inherit; lse itself is stored rounded (the backward reads it).
+#include <cfloat>
+
 #include "cs336/kernels.h"
 
 namespace cs336 {
 namespace {
 
 __device__ __forceinline__ void merge_ms(float& m, float& s, float m2, float s2) {
-  const float mn = fmaxf(m, m2);
-  if (mn == -INFINITY) return;
+  const float mn = fmaxf(m, m2);  // finite: both are >= the -FLT_MAX sentinel
   s = s * __expf(m - mn) + s2 * __expf(m2 - mn);
   m = mn;
 }
@@ -25,7 +32,7 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(const typename Elem<T>::s
   __shared__ float sm[4], ss[4];
   const int64_t row = blockIdx.x;
   const auto* zr = z + row * V;
-  float m = -INFINITY, s = 0.f;
+  float m = -FLT_MAX, s = 0.f;
   const bool vec = (V % 4 == 0);
   if (vec) {
     const int64_t V4 = V / 4;
@@ -62,9 +69,9 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(const typename Elem<T>::s
   if (threadIdx.x == 0) {
     float M_ = sm[0], S_ = ss[0];
     for (int i = 1; i < 4; ++i) merge_ms(M_, S_, sm[i], ss[i]);
-    const float l = M_ + __logf(S_);
-    lse[row] = l;
-    loss[row] = l - Elem<T>::to_f(zr[tgt[row]]);
+    const float ls = __logf(S_);
+    lse[row] = M_ + ls;
+    loss[row] = ls - (Elem<T>::to_f(zr[tgt[row]]) - M_);
   }
 }
 
