@@ -110,6 +110,13 @@ void fill_attn(cs336::AttnParams& p, const at::Tensor& q, const at::Tensor& k, c
 
 using OptT = std::optional<at::Tensor>;
 
+// What the last fa_fwd / fa_bwd call of this thread launched (host-side record for tests, read by
+// fa_last_launch): the forward's key splits; the backward form, numbered as CS336_FA_BWD numbers them
+// (0 two-kernel, 1 fused, 2 key-block parallel, 3 head-sequential), and the two-kernel form's key /
+// query splits. -1: no such call yet.
+thread_local int64_t fa_last_fwd_splits = -1;
+thread_local int64_t fa_last_bwd_form = -1, fa_last_bwd_ksplit = -1, fa_last_bwd_qsplit = -1;
+
 // fused RoPE: q/k are the un-rotated projections; cos/sin (ctx, D/2) fp32, pos (B, N) int64 or None
 void set_rope(cs336::AttnParams& p, const at::Tensor& q, const at::Tensor& k, const OptT& cos, const OptT& sin,
               const OptT& pos) {
@@ -158,6 +165,7 @@ std::tuple<at::Tensor, at::Tensor> fa_fwd(const at::Tensor& q, const at::Tensor&
     p.opart = ws.data_ptr<float>();
     p.lpart = p.opart + (int64_t)splits * p.B * p.H * p.Nq * p.D;
   }
+  fa_last_fwd_splits = splits;
   cs336::flash_attn_fwd(p, to_dtype(q), stream());
   return {o, lse};
 }
@@ -265,6 +273,7 @@ void fa_bwd_run(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k
     return e && *e ? std::atoi(e) : -1;
   }();
   const int64_t nbh = q.size(0) * q.size(1);
+  fa_last_bwd_ksplit = fa_last_bwd_qsplit = 1;
   // inverse RoPE of d(q|k) as one in-place pass after a kernel that returned them w.r.t. the rotated
   // inputs (dq and dk adjacent head blocks of one buffer -- the fused dQKV layout -- take one launch)
   auto rope_after_pass = [&]() {
@@ -295,6 +304,7 @@ void fa_bwd_run(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k
       hb.f.rope_out_only = false;
     }
     if (cs336::flash_attn_bwd_hs_ok(hb, to_dtype(q))) {
+      fa_last_bwd_form = 3;
       at::Tensor ws = at::empty({(int64_t)cs336::flash_attn_bwd_hs_workspace(hb)}, q.options().dtype(at::kFloat));
       cs336::flash_attn_bwd_hs(hb, to_dtype(q), ws.data_ptr<float>(), stream(), hr != 2);
       if (rope && hr == 0) rope_after_pass();
@@ -318,6 +328,7 @@ void fa_bwd_run(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k
       fb.f.rope_out_only = false;
     }
     if (cs336::flash_attn_bwd_fused_ok(fb, to_dtype(q))) {
+      fa_last_bwd_form = 1;
       cs336::flash_attn_bwd_fused(fb, to_dtype(q), stream());
       if (rope_after) rope_after_pass();
       return;
@@ -333,6 +344,7 @@ void fa_bwd_run(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k
   const bool kp_default = q.size(3) == 80 ||
       (q.size(3) == 64 && q.size(2) >= 2048 && q.size(0) * q.size(1) * ((q.size(2) + 255) / 256) >= 512);
   if ((mode == 2 || (mode < 0 && kp_default)) && cs336::flash_attn_bwd_kp_ok(bp, to_dtype(q))) {
+    fa_last_bwd_form = 2;
     at::Tensor ws = at::empty({(int64_t)cs336::flash_attn_bwd_kp_workspace(bp)}, q.options().dtype(at::kFloat));
     cs336::flash_attn_bwd_kp(bp, to_dtype(q), ws.data_ptr<float>(), stream());
     return;
@@ -361,7 +373,16 @@ void fa_bwd_run(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k
       bp.dv_part = w + n;
     }
   }
+  fa_last_bwd_form = 0;
+  fa_last_bwd_ksplit = ks;
+  fa_last_bwd_qsplit = qs;
   cs336::flash_attn_bwd(bp, to_dtype(q), stream());
+}
+
+// {forward splits, backward form, backward ksplit, backward qsplit} of this thread's last fa_fwd and
+// fa_bwd / fa_bwd_into calls (tests assert which kernel produced their numbers)
+std::vector<int64_t> fa_last_launch() {
+  return {fa_last_fwd_splits, fa_last_bwd_form, fa_last_bwd_ksplit, fa_last_bwd_qsplit};
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1464,6 +1485,7 @@ TORCH_LIBRARY(cs336, m) {
       "fa_decode(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_len, float scale, int max_kv_len, int splits=0) "
       "-> (Tensor o, Tensor lse)");
   m.def("fa_decode_splits(int B, int H, int D, int elem_size, int max_kv_len) -> int", &fa_decode_splits);
+  m.def("fa_last_launch() -> int[]", &fa_last_launch);
   m.def(
       "kv_append_rope(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor(a!) k_cache, Tensor(b!) v_cache) -> Tensor");
   m.def(

@@ -13,6 +13,14 @@ from cs336_systems.ops._ext import ops as _hip
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
+TWO_KERNEL, FUSED, KP, HS = 0, 1, 2, 3  # as CS336_FA_BWD numbers the backward forms
+
+
+def _ran(form):
+    """The backward form this thread's last fa_bwd / fa_bwd_into launched (a forced form falls through
+    to the next one when its *_ok() predicate refuses the call)."""
+    got = _hip().fa_last_launch()[1]
+    assert got == form, f"backward form {got} ran, not {form}"
 
 
 def _ref(q, k, v, do, causal):
@@ -42,6 +50,7 @@ def test_fused_bwd_vs_fp64(dt, causal, N, monkeypatch):
     hip = _hip()
     o, lse = hip.fa_fwd(q, k, v, causal, 0.125)
     dq, dk, dv = hip.fa_bwd(do, q, k, v, o, lse, causal, 0.125)
+    _ran(FUSED)
     rq, rk, rv = _ref(q, k, v, do, causal)
     for a, b, name in ((dq, rq, "dq"), (dk, rk, "dk"), (dv, rv, "dv")):
         err = (a.double() - b).abs().max().item()
@@ -58,8 +67,10 @@ def test_fused_matches_two_kernel(causal, N, monkeypatch):
     o, lse = hip.fa_fwd(q, k, v, causal, 0.125)
     monkeypatch.setenv("CS336_FA_BWD", "0")
     two = hip.fa_bwd(do, q, k, v, o, lse, causal, 0.125)
+    _ran(TWO_KERNEL)
     monkeypatch.setenv("CS336_FA_BWD", "1")
     fused = hip.fa_bwd(do, q, k, v, o, lse, causal, 0.125)
+    _ran(FUSED)
     again = hip.fa_bwd(do, q, k, v, o, lse, causal, 0.125)
     for a, b, c in zip(fused, two, again):
         assert torch.equal(a, c)  # deterministic: no atomics
@@ -90,12 +101,16 @@ def test_fused_rope_out_only_in_step_layout(monkeypatch):
     monkeypatch.delenv("CS336_FA_BWD", raising=False)
     monkeypatch.delenv("CS336_FA_HS_ROPE", raising=False)
     default = run()
+    _ran(HS)
     monkeypatch.setenv("CS336_FA_BWD", "3")
     hs = run()
+    _ran(HS)
     monkeypatch.setenv("CS336_FA_BWD", "1")
     fused = run()
+    _ran(FUSED)
     monkeypatch.setenv("CS336_FA_BWD", "0")
     two = run()
+    _ran(TWO_KERNEL)
     assert torch.equal(default, hs)
     torch.testing.assert_close(fused.float(), two.float(), rtol=2e-2, atol=2e-2)
     torch.testing.assert_close(hs.float(), two.float(), rtol=2e-2, atol=2e-2)
@@ -123,6 +138,7 @@ def test_kp_bwd_vs_fp64(dt, causal, N, D, waves, monkeypatch):
     sc = D**-0.5
     o, lse = hip.fa_fwd(q, k, v, causal, sc)
     dq, dk, dv = hip.fa_bwd(do, q, k, v, o, lse, causal, sc)
+    _ran(KP)
     rq, rk, rv = _ref(q, k, v, do, causal)
     for a, b, name in ((dq, rq, "dq"), (dk, rk, "dk"), (dv, rv, "dv")):
         assert torch.isfinite(a).all(), name
@@ -145,9 +161,11 @@ def test_kp_slabs_vs_atomics(causal, N, D, monkeypatch):
     sc = D**-0.5
     o, lse = hip.fa_fwd(q, k, v, causal, sc)
     slab = hip.fa_bwd(do, q, k, v, o, lse, causal, sc)
+    _ran(KP)
     again = hip.fa_bwd(do, q, k, v, o, lse, causal, sc)
     monkeypatch.setenv("CS336_FA_KP_SLAB", "0")
     atom = hip.fa_bwd(do, q, k, v, o, lse, causal, sc)
+    _ran(KP)
     for a, b in zip(slab, again):
         assert torch.equal(a, b)
     assert torch.equal(slab[1], atom[1]) and torch.equal(slab[2], atom[2])
@@ -169,9 +187,11 @@ def test_kp_matches_two_kernel_long(causal, D, waves, monkeypatch):
     o, lse = hip.fa_fwd(q, k, v, causal, D**-0.5)
     monkeypatch.setenv("CS336_FA_BWD", "0")
     two = hip.fa_bwd(do, q, k, v, o, lse, causal, D**-0.5)
+    _ran(TWO_KERNEL)
     monkeypatch.setenv("CS336_FA_BWD", "2")  # key-block parallel (the default only at d 80)
     monkeypatch.setenv("CS336_FA_KP_WAVES", str(waves))
     kp = hip.fa_bwd(do, q, k, v, o, lse, causal, D**-0.5)
+    _ran(KP)
     for a, b in zip(kp, two):
         torch.testing.assert_close(a.float(), b.float(), rtol=2e-2, atol=2e-2)
 
@@ -186,10 +206,13 @@ def test_default_long_d64_selects_kp(causal, monkeypatch):
     o, lse = hip.fa_fwd(q, k, v, causal, D**-0.5)
     monkeypatch.delenv("CS336_FA_BWD", raising=False)
     default = hip.fa_bwd(do, q, k, v, o, lse, causal, D**-0.5)
+    _ran(KP)
     monkeypatch.setenv("CS336_FA_BWD", "2")
     kp = hip.fa_bwd(do, q, k, v, o, lse, causal, D**-0.5)
+    _ran(KP)
     monkeypatch.setenv("CS336_FA_BWD", "0")
     two = hip.fa_bwd(do, q, k, v, o, lse, causal, D**-0.5)
+    _ran(TWO_KERNEL)
     for a, b, c in zip(default, kp, two):
         # dK / dV have no atomics: the default is the key-block-parallel kernel bit for bit
         torch.testing.assert_close(a.float(), c.float(), rtol=2e-2, atol=2e-2)
@@ -218,8 +241,10 @@ def test_kp_rope_out_only_in_step_layout(D, monkeypatch):
 
     monkeypatch.setenv("CS336_FA_BWD", "2")
     kp = run()
+    _ran(KP)
     monkeypatch.setenv("CS336_FA_BWD", "0")
     two = run()
+    _ran(TWO_KERNEL)
     torch.testing.assert_close(kp.float(), two.float(), rtol=2e-2, atol=2e-2)
 
 
@@ -234,6 +259,7 @@ def test_hs_bwd_vs_fp64(dt, causal, N, monkeypatch):
     hip = _hip()
     o, lse = hip.fa_fwd(q, k, v, causal, 0.125)
     dq, dk, dv = hip.fa_bwd(do, q, k, v, o, lse, causal, 0.125)
+    _ran(HS)
     again = hip.fa_bwd(do, q, k, v, o, lse, causal, 0.125)
     rq, rk, rv = _ref(q, k, v, do, causal)
     for a, b, c, name in ((dq, rq, again[0], "dq"), (dk, rk, again[1], "dk"), (dv, rv, again[2], "dv")):
@@ -266,8 +292,10 @@ def test_hs_rope_out_only_in_step_layout(rope_in_kernel, monkeypatch):
     monkeypatch.setenv("CS336_FA_HS_ROPE", rope_in_kernel)
     monkeypatch.setenv("CS336_FA_BWD", "3")
     hs = run()
+    _ran(HS)
     monkeypatch.setenv("CS336_FA_BWD", "0")
     two = run()
+    _ran(TWO_KERNEL)
     torch.testing.assert_close(hs.float(), two.float(), rtol=2e-2, atol=2e-2)
 
 
@@ -282,7 +310,9 @@ def test_hs_in_kernel_delta_matches_prep(causal, N, monkeypatch):
     hip = _hip()
     o, lse = hip.fa_fwd(q, k, v, causal, 0.125)
     ind = hip.fa_bwd(do, q, k, v, o, lse, causal, 0.125)
+    _ran(HS)
     monkeypatch.setenv("CS336_FA_HS_DELTA", "0")
     prep = hip.fa_bwd(do, q, k, v, o, lse, causal, 0.125)
+    _ran(HS)
     for a, b in zip(ind, prep):
         assert torch.equal(a, b)
