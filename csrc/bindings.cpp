@@ -80,10 +80,7 @@ void fill_attn(cs336::AttnParams& p, const at::Tensor& q, const at::Tensor& k, c
   p.scale = (float)scale;
   p.causal = causal;
   // CS336_FA_ORDER=0 restores the per-head interleaved block order (A/B switch for tile_order)
-  static const int order = [] {
-    const char* e = std::getenv("CS336_FA_ORDER");
-    return e ? std::atoi(e) : 1;
-  }();
+  static const int order = cs336::env_int("CS336_FA_ORDER", 1, /*empty_is_unset=*/false);
   p.order = order;
   // heads whose K+V fit one XCD's 4 MB L2 form one level-major group (tile_order, fa_common.h)
   const int64_t kv_head = 2 * (int64_t)p.Nk * p.D * (int64_t)q.element_size();
@@ -93,10 +90,7 @@ void fill_attn(cs336::AttnParams& p, const at::Tensor& q, const at::Tensor& k, c
   // N 4096 +7.5 %, d80 causal N 1024 +5 %, d64 causal N 512 -1.3 %, profiles/r2_fa_bwd_valu.md); the
   // backward kernels lose 2-7 % (their time is not in the tile loads). CS336_FA_DMA: unset = that
   // choice, 0 = never, 1 = every forward, 2 = forward and backward.
-  const int dma_env = [] {  // read per call (cheap next to a launch): tests switch it in-process
-    const char* e = std::getenv("CS336_FA_DMA");
-    return e && *e ? std::atoi(e) : -1;
-  }();
+  const int dma_env = cs336::env_int("CS336_FA_DMA", -1);  // per call: tests switch it in-process
   // 4: the forward's pipelined variant (separate K/V rings, next S^T inside this tile's softmax)
   // backward (bit 2): with the dQ / dK-dV DMA loops unrolled by their ring depth LDS-DMA staging
   // wins at Nk >= 1024 (d 64 +5 %, d 128 +5-10 %, d 80 even); it loses 2 % at the XL step's N 512
@@ -153,10 +147,7 @@ std::tuple<at::Tensor, at::Tensor> fa_fwd(const at::Tensor& q, const at::Tensor&
   fill_attn(p, q, k, v, o, lse, causal, scale);
   set_rope(p, q, k, rope_cos, rope_sin, rope_pos);
   // split-KV when the query blocks cannot fill the chip (CS336_FA_SPLITS=n forces n, 1 = off)
-  const int force_splits = [] {  // read per call (cheap next to a launch): tests switch it in-process
-    const char* e = std::getenv("CS336_FA_SPLITS");
-    return e && *e ? std::atoi(e) : 0;
-  }();
+  const int force_splits = cs336::env_int("CS336_FA_SPLITS", 0);  // per call: tests switch it in-process
   const int splits = force_splits > 0 ? force_splits : cs336::flash_attn_fwd_splits(p);
   at::Tensor ws;
   if (splits > 1) {
@@ -242,6 +233,15 @@ void fa_bwd_into(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& 
   fa_bwd_run(dout, q, k, v, out, lse, causal, scale, dq, dk, dv, rope_cos, rope_sin, rope_pos, rope_out_only);
 }
 
+// bp for a kernel that returns dq / dk w.r.t. the rotated q, k: the caller strips the RoPE here and
+// rotates them back in a pass of its own
+cs336::AttnBwdParams without_rope(cs336::AttnBwdParams bp) {
+  bp.f.rope_cos = bp.f.rope_sin = nullptr;
+  bp.f.rope_pos = nullptr;
+  bp.f.rope_out_only = false;
+  return bp;
+}
+
 void fa_bwd_run(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                 const at::Tensor& out, const at::Tensor& lse, bool causal, double scale, const at::Tensor& dq,
                 const at::Tensor& dk, const at::Tensor& dv, const OptT& rope_cos, const OptT& rope_sin,
@@ -268,10 +268,7 @@ void fa_bwd_run(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k
   //   1: head-sequential wherever it applies (then as unset); 2: key-block parallel wherever it
   //   applies; 0: the two-kernel form (dQ kernel + dK/dV kernel: deterministic, any shape);
   //   3: the two-workgroups-per-CU head-sequential kernel (fa_bwd_hs.hip) where it applies.
-  const int mode = [] {
-    const char* e = std::getenv("CS336_FA_BWD");
-    return e && *e ? std::atoi(e) : -1;
-  }();
+  const int mode = cs336::env_int("CS336_FA_BWD", -1);
   const int64_t nbh = q.size(0) * q.size(1);
   fa_last_bwd_ksplit = fa_last_bwd_qsplit = 1;
   // inverse RoPE of d(q|k) as one in-place pass after a kernel that returned them w.r.t. the rotated
@@ -294,15 +291,9 @@ void fa_bwd_run(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k
   // both dQ and dK by the pass, 1 both in the kernel's stores, 2 dK in the kernel (at the key-block
   // switch, where it drains anyway) and dQ by the pass
   if (mode == 3 || (mode < 0 && nbh >= 512 && q.size(2) <= 1024)) {
-    const char* re = std::getenv("CS336_FA_HS_ROPE");
-    const int hr = re && *re ? std::atoi(re) : 0;
+    const int hr = cs336::env_int("CS336_FA_HS_ROPE", 0);
     const bool rope = bp.f.rope_out_only;
-    cs336::AttnBwdParams hb = bp;
-    if (rope && hr == 0) {
-      hb.f.rope_cos = hb.f.rope_sin = nullptr;
-      hb.f.rope_pos = nullptr;
-      hb.f.rope_out_only = false;
-    }
+    const cs336::AttnBwdParams hb = rope && hr == 0 ? without_rope(bp) : bp;
     if (cs336::flash_attn_bwd_hs_ok(hb, to_dtype(q))) {
       fa_last_bwd_form = 3;
       at::Tensor ws = at::empty({(int64_t)cs336::flash_attn_bwd_hs_workspace(hb)}, q.options().dtype(at::kFloat));
@@ -321,12 +312,7 @@ void fa_bwd_run(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k
     // kernel: a rotating store inside it measured slower (0.430 vs 0.373 ms at the XL shape in the
     // step's fused-QKV layout, scripts/fa_step_layout.py; profiles/r3_qkv_rope_ab.md)
     const bool rope_after = bp.f.rope_out_only;
-    cs336::AttnBwdParams fb = bp;
-    if (rope_after) {
-      fb.f.rope_cos = fb.f.rope_sin = nullptr;
-      fb.f.rope_pos = nullptr;
-      fb.f.rope_out_only = false;
-    }
+    const cs336::AttnBwdParams fb = rope_after ? without_rope(bp) : bp;
     if (cs336::flash_attn_bwd_fused_ok(fb, to_dtype(q))) {
       fa_last_bwd_form = 1;
       cs336::flash_attn_bwd_fused(fb, to_dtype(q), stream());
@@ -355,8 +341,7 @@ void fa_bwd_run(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k
   // low parallelism: split the dQ kernel over keys and the dK/dV kernel over queries (fp32 partial
   // slabs + reduce); CS336_FA_BWD_SPLITS=1 turns it off
   int ks = 1, qs = 1;
-  const char* se = std::getenv("CS336_FA_BWD_SPLITS");
-  if (!(se && *se && std::atoi(se) == 1)) cs336::flash_attn_bwd_splits(bp, ks, qs);
+  if (cs336::env_int("CS336_FA_BWD_SPLITS", 0) != 1) cs336::flash_attn_bwd_splits(bp, ks, qs);
   at::Tensor parts;
   if (ks > 1 || qs > 1) {
     parts = at::empty({(int64_t)cs336::flash_attn_bwd_split_workspace(bp, ks, qs)}, q.options().dtype(at::kFloat));

@@ -29,7 +29,7 @@
 //   while waves 4-7 compute the next slice's delta during the first key block.
 // delta = rowsum(dO·O) is computed in the first key block's pass (registers prefetched one slice
 // ahead) and kept with -lse·log2(e) for the whole head in LDS (N ≤ 1024).
-#include "fa_common.h"
+#include "fa_bwd_common.h"
 
 namespace cs336 {
 namespace fa {
@@ -37,7 +37,7 @@ namespace fa {
 namespace {
 constexpr int FD = 64;            // head dim
 constexpr int FRB = FD * 2;       // 128-B image rows
-constexpr int FBQ = 64;           // query slice
+constexpr int FBQ = kBwdBQ;       // query slice
 constexpr int FKB = 256;          // keys per block: 4 waves x 2 groups x 32
 constexpr int FTILE = FBQ * FRB;  // 8 KiB
 constexpr int FSLOT = 2 * FTILE;  // Q, dO images
@@ -83,29 +83,15 @@ __global__ __launch_bounds__(512, 1) void fa_bwd_fused_kernel(const AttnBwdParam
   // row fragments (A/B operand with the image row on the lane): rows 32t + l32, chunk 2ks + hh
   const int swl = swz<FRB>(l32);
   uint32_t roff[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) roff[ks] = l32 * FRB + (((2 * ks + hh) ^ swl) << 4);
-  // transposed fragments (ds_read_b64_tr_b16, see lds_tr_frag): rows 16s + tra (+8), column tile dt
-  const int ti = lane & 15, tra = 4 * hh + (ti >> 2), tcl = ((lane >> 4) & 1) * 2 + ((ti & 3) >> 1);
-  const int swa = swz<FRB>(tra), swb = swz<FRB>(tra + 8);
+  row_offsets<FRB>(l32, hh, roff);
+  // transposed fragments (tr_offsets): rows 16s + 4hh + ((lane&15)>>2) (+8), column tile dt
   uint32_t toa[2], tob[2];
 #pragma unroll
-  for (int dt = 0; dt < 2; ++dt) {
-    toa[dt] = tra * FRB + ((((dt << 2) | tcl) ^ swa) << 4) + (ti & 1) * 8;
-    tob[dt] = (tra + 8) * FRB + ((((dt << 2) | tcl) ^ swb) << 4) + (ti & 1) * 8;
-  }
+  for (int dt = 0; dt < 2; ++dt) tr_offsets<FRB>(lane, dt, toa[dt], tob[dt]);
   auto rowf = [&](const char* img, int ks) -> F {
     return as_frag<T>(*reinterpret_cast<const uint4*>(img + roff[ks]));
   };
-  auto trf2 = [&](const char* img, uint32_t oa, uint32_t ob) -> F {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + oa));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + ob));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(F, v);
-  };
+  auto trf2 = [&](const char* img, uint32_t oa, uint32_t ob) -> F { return lds_tr_read<T>(img, oa, ob); };
   auto trf = [&](const char* img, int dt) -> F { return trf2(img, toa[dt], tob[dt]); };
 
   // ---- LDS-DMA: wave-instruction i of a tile moves rows 64i + 8 wave + (lane>>3), physical chunk
@@ -148,15 +134,7 @@ __global__ __launch_bounds__(512, 1) void fa_bwd_fused_kernel(const AttnBwdParam
     po[1] = *reinterpret_cast<const uint4*>(Op + row * o_sn + e + 8);
     float acc = 0.f;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const uint32_t a[4] = {pd[i].x, pd[i].y, pd[i].z, pd[i].w};
-      const uint32_t c[4] = {po[i].x, po[i].y, po[i].z, po[i].w};
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        acc = fmaf(Elem<T>::to_f((S)(a[w] & 0xffff)), Elem<T>::to_f((S)(c[w] & 0xffff)), acc);
-        acc = fmaf(Elem<T>::to_f((S)(a[w] >> 16)), Elem<T>::to_f((S)(c[w] >> 16)), acc);
-      }
-    }
+    for (int i = 0; i < 2; ++i) acc = dot8<T>(pd[i], po[i], acc);
     acc += __shfl_xor(acc, 1, 64);
     acc += __shfl_xor(acc, 2, 64);
     if ((pt & 3) == 0) Dh[s * FBQ + row_perm(pt >> 2)] = -acc;
@@ -184,15 +162,7 @@ __global__ __launch_bounds__(512, 1) void fa_bwd_fused_kernel(const AttnBwdParam
     if (key >= N) return;
     S* rk = (S*)bp.dk + b * bp.dk_sb + h * bp.dk_sh + key * dk_sn;
     S* rv = (S*)bp.dv + b * bp.dv_sb + h * bp.dv_sh + key * dv_sn;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const int d = 32 * dt + 8 * g4 + 4 * hh;
-        store4<T>(rk + d, make_float4(dk[dt][4 * g4] * sc, dk[dt][4 * g4 + 1] * sc, dk[dt][4 * g4 + 2] * sc,
-                                      dk[dt][4 * g4 + 3] * sc));
-        store4<T>(rv + d, make_float4(dv[dt][4 * g4], dv[dt][4 * g4 + 1], dv[dt][4 * g4 + 2], dv[dt][4 * g4 + 3]));
-      }
+    store_dkdv<T, 2, false>(dk, dv, rk, rv, sc, Rope{}, 0, hh);
   };
 
   // ---- dQ (waves 0-3): tile d rows 32 dqt.., queries 32 qqt.. ---------------------------------
@@ -329,15 +299,7 @@ __global__ __launch_bounds__(512, 1) void fa_bwd_fused_kernel(const AttnBwdParam
           for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) dk[dt] = Mma16<T>::mma(qt[s2][dt], sf[s2], dk[dt]);
-          // dSᵀ row (block-local key 32g + l32, swizzle swl): the fragment's two 4-query halves are
-          // q = 32t + 16s2 + 4hh + 0..3 and the same + 8 (pack_acc order), one 8-B write each
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2) {
-            const uint4 w = __builtin_bit_cast(uint4, sf[s2]);
-            const int ch = 4 * t + 2 * s2;
-            *reinterpret_cast<uint2*>(drow + ((ch ^ swl) << 4)) = make_uint2(w.x, w.y);
-            *reinterpret_cast<uint2*>(drow + (((ch + 1) ^ swl) << 4)) = make_uint2(w.z, w.w);
-          }
+          store_dst(drow, swl, t, sf);  // dSᵀ row (block-local key 32g + l32, swizzle swl)
         }
       }
       dma_barrier();  // dSᵀ of every group written
@@ -358,6 +320,8 @@ __global__ __launch_bounds__(512, 1) void fa_bwd_fused_kernel(const AttnBwdParam
             dq = Mma16<T>::mma(trf2(Kimg + ro, kqa, kqb), trf2(dsimg + ro, dsa, dsb), dq);
           }
         }
+        // (this store block is the same in fa_bwd_hs.hip and fa_bwd_fused.hip; a shared helper changed
+        // both kernels' register counts, so each keeps its copy)
         // H: store (lane = query row qrow, registers 4g4..4g4+3 = d 32dqt + 8g4 + 4hh + 0..3)
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {

@@ -37,7 +37,7 @@
 // just finished reading. The compiler's own wait for the partial loads (it cannot see the DMA) also
 // retires item j + 1's DMA, issued an item earlier; without partial loads the next item waits for
 // everything but this item's stores and DMA (4 + its DMA count). A key-block switch drains to 0.
-#include "fa_common.h"
+#include "fa_bwd_common.h"
 
 namespace cs336 {
 namespace fa {
@@ -45,7 +45,7 @@ namespace fa {
 namespace {
 constexpr int HS_D = 64;
 constexpr int HS_RB = HS_D * 2;              // 128-B image rows
-constexpr int HS_BQ = 64;                    // query slice
+constexpr int HS_BQ = kBwdBQ;                // query slice
 constexpr int HS_KB = 128;                   // keys per block: 4 waves x 32
 constexpr int HS_TILE = HS_BQ * HS_RB;       // 8 KiB
 constexpr int HS_SLOT = 2 * HS_TILE + 1024;  // Q | dO | row constants (512 B used)
@@ -64,10 +64,7 @@ static_assert(HS_LDS_IND <= 80 * 1024, "two workgroups per CU");
 constexpr int HS_SLICE_DMA = 2 * (HS_BQ * (HS_RB / 16) / 256);  // Q + dO wave-instructions per wave
 
 // CS336_FA_HS_DELTA=0: row constants from the prep kernel instead of the in-kernel delta
-inline bool hs_in_kernel_delta() {
-  const char* e = getenv("CS336_FA_HS_DELTA");
-  return !(e && *e && atoi(e) == 0);
-}
+inline bool hs_in_kernel_delta() { return env_int("CS336_FA_HS_DELTA", 1) != 0; }
 
 // wait until at most n of this wave's vector memory operations are outstanding (n wave-uniform;
 // the counts that occur: 4 + {0, 4, 5})
@@ -79,44 +76,15 @@ __device__ __forceinline__ void wait_vm_upto(int n) {
 }
 }  // namespace
 
-// ---- (1) row constants -----------------------------------------------------------------------
-// block = (head, 64-row slice); 4 threads per row, 16 d each
-template <typename T>
-__global__ __launch_bounds__(256) void fa_bwd_hs_prep(const AttnBwdParams bp, float* __restrict__ rowc) {
-  typedef typename Elem<T>::storage S;
-  const int N = bp.f.Nq, nqs = N / HS_BQ;
-  const int bh = blockIdx.x / nqs, s = blockIdx.x % nqs;
-  const int b = bh / bp.f.H, h = bh % bp.f.H;
-  const int tid = threadIdx.x, r = tid >> 2, k = tid & 3, row = s * HS_BQ + r;
-  const S* o = (const S*)bp.f.o + b * bp.f.o_sb + h * bp.f.o_sh + (int64_t)row * bp.f.o_sn + 16 * k;
-  const S* g = (const S*)bp.dout + b * bp.do_sb + h * bp.do_sh + (int64_t)row * bp.do_sn + 16 * k;
-  const uint4 uo[2] = {*reinterpret_cast<const uint4*>(o), *reinterpret_cast<const uint4*>(o + 8)};
-  const uint4 ug[2] = {*reinterpret_cast<const uint4*>(g), *reinterpret_cast<const uint4*>(g + 8)};
-  float dsum = 0.f;
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const uint32_t wo[4] = {uo[c].x, uo[c].y, uo[c].z, uo[c].w}, wg[4] = {ug[c].x, ug[c].y, ug[c].z, ug[c].w};
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      dsum = fmaf(Elem<T>::to_f((S)(wo[w] & 0xffff)), Elem<T>::to_f((S)(wg[w] & 0xffff)), dsum);
-      dsum = fmaf(Elem<T>::to_f((S)(wo[w] >> 16)), Elem<T>::to_f((S)(wg[w] >> 16)), dsum);
-    }
-  }
-  dsum += __shfl_xor(dsum, 1, 64);
-  dsum += __shfl_xor(dsum, 2, 64);
-  if (k == 0) {
-    float* rc = rowc + ((int64_t)bh * nqs + s) * 128;
-    rc[row_perm(r)] = -bp.f.lse[(int64_t)bh * N + row] * kLog2e;
-    rc[64 + row_perm(r)] = -dsum;
-  }
-}
+// ---- (1) row constants: fa_bwd_rowc_prep (fa_bwd_common.h), chunks 2k, 2k+1 per thread as delta_slice
+// below ------------------------------------------------------------------------------------------
 
 // ---- (2) main kernel -------------------------------------------------------------------------
 // ROPE: 0 = none, 1 = inverse rotation in the dQ and dK stores, 2 = in the dK stores only (the caller
 // rotates dQ back in a separate pass). IND: delta = rowsum(dO·O) computed here during the first key
 // block's pass (O slices staged by LDS-DMA one item ahead, -delta of the head kept in LDS) and the
 // row's lse staged raw with each slice -- no prep kernel, no second read of dO; else the row
-// constants come from fa_bwd_hs_prep (rowc).
+// constants come from fa_bwd_rowc_prep (rowc).
 template <typename T, bool CAUSAL, int ROPE, bool IND>
 __global__ __launch_bounds__(256, 2) void fa_bwd_hs_kernel(const AttnBwdParams bp, const float* __restrict__ rowc,
                                                            float* __restrict__ part_all) {
@@ -141,28 +109,12 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_hs_kernel(const AttnBwdParams b
   // ---- per-lane LDS offsets (row bases are multiples of 16 rows: the swizzle is the lane's) ----
   const int swl = swz<HS_RB>(l32);
   uint32_t roff[4];  // row fragments: row l32, chunk 2ks + hh
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) roff[ks] = (uint32_t)(l32 * HS_RB + (((2 * ks + hh) ^ swl) << 4));
+  row_offsets<HS_RB>(l32, hh, roff);
   uint32_t toa[2], tob[2];  // transposed fragments of 32-column tile c of a 128-B-row image
-  {
-    const int ti = lane & 15, tra = 4 * hh + (ti >> 2), tcl = ((lane >> 4) & 1) * 2 + ((ti & 3) >> 1);
-    const int swa = swz<HS_RB>(tra), swb = swz<HS_RB>(tra + 8);
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      toa[c] = (uint32_t)(tra * HS_RB + ((((c << 2) | tcl) ^ swa) << 4) + (ti & 1) * 8);
-      tob[c] = (uint32_t)((tra + 8) * HS_RB + ((((c << 2) | tcl) ^ swb) << 4) + (ti & 1) * 8);
-    }
-  }
+  for (int c = 0; c < 2; ++c) tr_offsets<HS_RB>(lane, c, toa[c], tob[c]);
   auto rowf = [&](const char* img, int ks) -> F { return as_frag<T>(*reinterpret_cast<const uint4*>(img + roff[ks])); };
-  auto trf2 = [&](const char* img, uint32_t oa, uint32_t ob) -> F {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + oa));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + ob));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(F, v);
-  };
+  auto trf2 = [&](const char* img, uint32_t oa, uint32_t ob) -> F { return lds_tr_read<T>(img, oa, ob); };
 
   // ---- LDS-DMA staging ---------------------------------------------------------------------------
   TileDma<HS_BQ, HS_RB, 8, 2> dq_, dd_;
@@ -196,16 +148,9 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_hs_kernel(const AttnBwdParams b
     const int r = tid >> 2, k = tid & 3;
     float acc = 0.f;
 #pragma unroll
-    for (int c = 2 * k; c < 2 * k + 2; ++c) {
-      const uint4 ug = *reinterpret_cast<const uint4*>(dOs + lds_off<HS_RB>(r, c));
-      const uint4 uo = *reinterpret_cast<const uint4*>(Oimg + lds_off<HS_RB>(r, c));
-      const uint32_t wg[4] = {ug.x, ug.y, ug.z, ug.w}, wo[4] = {uo.x, uo.y, uo.z, uo.w};
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        acc = fmaf(Elem<T>::to_f((S)(wg[w] & 0xffff)), Elem<T>::to_f((S)(wo[w] & 0xffff)), acc);
-        acc = fmaf(Elem<T>::to_f((S)(wg[w] >> 16)), Elem<T>::to_f((S)(wo[w] >> 16)), acc);
-      }
-    }
+    for (int c = 2 * k; c < 2 * k + 2; ++c)
+      acc = dot8<T>(*reinterpret_cast<const uint4*>(dOs + lds_off<HS_RB>(r, c)),
+                    *reinterpret_cast<const uint4*>(Oimg + lds_off<HS_RB>(r, c)), acc);
     acc += __shfl_xor(acc, 1, 64);
     acc += __shfl_xor(acc, 2, 64);
     if (k == 0) Dh[s * HS_BQ + row_perm(r)] = -acc;
@@ -239,17 +184,7 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_hs_kernel(const AttnBwdParams b
     S* rk = (S*)bp.dk + b * bp.dk_sb + h * bp.dk_sh + (int64_t)key * bp.dk_sn;
     S* rv = (S*)bp.dv + b * bp.dv_sb + h * bp.dv_sh + (int64_t)key * bp.dv_sn;
     const int64_t pos = ROPE != 0 ? (bp.f.rope_pos ? bp.f.rope_pos[(int64_t)b * N + key] : key) : 0;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const int d = 32 * dt + 8 * g4 + 4 * hh;
-        float k0 = dk[dt][4 * g4] * sc, k1 = dk[dt][4 * g4 + 1] * sc, k2 = dk[dt][4 * g4 + 2] * sc,
-              k3 = dk[dt][4 * g4 + 3] * sc;
-        if constexpr (ROPE != 0) rope_inv4(k0, k1, k2, k3, rope, pos, d);
-        store4<T>(rk + d, make_float4(k0, k1, k2, k3));
-        store4<T>(rv + d, make_float4(dv[dt][4 * g4], dv[dt][4 * g4 + 1], dv[dt][4 * g4 + 2], dv[dt][4 * g4 + 3]));
-      }
+    store_dkdv<T, 2, ROPE != 0>(dk, dv, rk, rv, sc, rope, pos, hh);
   };
 
   // dQᵀ tile of this wave: d rows 32 dqt.., queries 32 qqt..
@@ -363,14 +298,7 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_hs_kernel(const AttnBwdParams b
               dk[dt] = Mma16<T>::mma(qt[s2], sf[s2], dk[dt]);
             }
           }
-          // dSᵀ row (block-local key 32 wave + l32): query halves 32t + 16s2 + 4hh + 0..3 and + 8
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2) {
-            const uint4 w = __builtin_bit_cast(uint4, sf[s2]);
-            const int ch = 4 * t + 2 * s2;
-            *reinterpret_cast<uint2*>(drow + ((ch ^ swl) << 4)) = make_uint2(w.x, w.y);
-            *reinterpret_cast<uint2*>(drow + (((ch + 1) ^ swl) << 4)) = make_uint2(w.z, w.w);
-          }
+          store_dst(drow, swl, t, sf);  // dSᵀ row (block-local key 32 wave + l32)
         }
       }
       dma_barrier();  // D: dSᵀ of every group written, every wave done with this slot
@@ -387,6 +315,8 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_hs_kernel(const AttnBwdParams b
             dq = Mma16<T>::mma(trf2(Kimg + ro, toa[dqt], tob[dqt]), trf2(dsimg + ro, toa[qqt], tob[qqt]), dq);
           }
         }
+        // (this store block is the same in fa_bwd_hs.hip and fa_bwd_fused.hip; a shared helper changed
+        // both kernels' register counts, so each keeps its copy)
         // F: store (lane = query row qrow, registers 4g4..4g4+3 = d 32dqt + 8g4 + 4hh + 0..3)
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
@@ -453,7 +383,8 @@ void launch_hs(const AttnBwdParams& bp, float* rowc, float* part, hipStream_t s)
       return;
     }
   }
-  hipLaunchKernelGGL((fa_bwd_hs_prep<T>), dim3((unsigned)(BH * (N / HS_BQ))), dim3(256), 0, s, bp, rowc);
+  hipLaunchKernelGGL((fa_bwd_rowc_prep<T, HS_D, true, false>), dim3((unsigned)(BH * (N / HS_BQ))), dim3(256), 0, s, bp,
+                     rowc, (float*)nullptr);
   hipLaunchKernelGGL((fa_bwd_hs_kernel<T, C, R, false>), dim3((unsigned)BH), dim3(256), 0, s, bp, rowc, part);
 }
 

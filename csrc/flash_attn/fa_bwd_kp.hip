@@ -38,31 +38,28 @@
 // stage the slices (TileDma's 4 x 64-lane rounds); with 8 waves, waves 4-7 issue no DMA.
 // Causal: key block 0 (the heaviest) of every head is dispatched first; the slices start at the
 // block's diagonal and only diagonal tiles are masked.
-#include "fa_common.h"
+#include "fa_bwd_common.h"
 
 namespace cs336 {
 namespace fa {
 
 namespace {
 constexpr int KP_KB = 256;  // keys per workgroup
-constexpr int KP_BQ = 64;   // query slice
+constexpr int KP_BQ = kBwdBQ;  // query slice
 constexpr int64_t KP_SLAB_LIMIT = (int64_t)4 << 30;  // bytes of dQ slabs before the atomic fallback
 
 // waves per workgroup: 4 (one per SIMD, 64 keys = two 32-key groups each) or 8 (two per SIMD, one group
 // each: a second wave on every SIMD covers the first one's LDS and barrier latencies): 8 by default,
 // 1.15-1.45x the 4-wave form at every measured shape (profiles/r6_fa_kp_waves.md; the d 80 non-causal
 // build spills 13-15 registers and still wins); CS336_FA_KP_WAVES=4 selects the 4-wave form.
-inline int kp_waves(const AttnBwdParams&) {
-  const char* e = getenv("CS336_FA_KP_WAVES");
-  return (e && *e && atoi(e) == 4) ? 4 : 8;
-}
+inline int kp_waves(const AttnBwdParams&) { return env_int("CS336_FA_KP_WAVES", 8) == 4 ? 4 : 8; }
 
 inline int kp_nkb(const AttnBwdParams& bp) { return (bp.f.Nq + KP_KB - 1) / KP_KB; }
 // slabs up to 4 key blocks (N <= 1024): B 32 H 32 N 1024 d 80 causal 1.11 vs 1.16 ms with atomics;
 // at N 4096 (16 blocks; the convert then reads 8.5 slabs per row) atomics win, 0.70 vs 0.80 ms
 // (profiles/r6_fa_kp_waves.md). CS336_FA_KP_SLAB=0|1 forces one (slabs only within KP_SLAB_LIMIT).
 inline bool kp_slabs(const AttnBwdParams& bp) {
-  const char* e = getenv("CS336_FA_KP_SLAB");
+  const char* e = getenv("CS336_FA_KP_SLAB");  // read by hand: unset means a choice, not a number
   const bool want = (e && *e) ? atoi(e) != 0 : kp_nkb(bp) <= 4;
   return want && (int64_t)kp_nkb(bp) * bp.f.B * bp.f.H * bp.f.Nq * bp.f.D * 4 <= KP_SLAB_LIMIT;
 }
@@ -92,55 +89,10 @@ struct KpGeo {
   static constexpr int inflight(int w) { return 16 * tiles(w) + SLICE_DMA + (w == 0 ? 1 : 0); }
   static_assert(inflight(0) <= 63, "vmcnt range");
 };
-
-// transposed-fragment offsets (ds_read_b64_tr_b16 pair, see lds_tr_frag) of column tile c (32
-// elements) in an image with R-byte rows, for a row base that is a multiple of 16 rows
-template <int R>
-__device__ __forceinline__ void tr_offsets(int lane, int c, uint32_t& oa, uint32_t& ob) {
-  const int hh = lane >> 5, ti = lane & 15;
-  const int tra = 4 * hh + (ti >> 2), tcl = ((lane >> 4) & 1) * 2 + ((ti & 3) >> 1);
-  const int ch = (c << 2) | tcl;
-  oa = (uint32_t)(tra * R + ((ch ^ swz<R>(tra)) << 4) + (ti & 1) * 8);
-  ob = (uint32_t)((tra + 8) * R + ((ch ^ swz<R>(tra + 8)) << 4) + (ti & 1) * 8);
-}
 }  // namespace
 
-// ---- (1) row constants + zeroed dQ accumulator ------------------------------------------------
-// block = (head, 64-row slice); 4 threads per row, each over 16-B chunks c, c+4, ... of d
-template <typename T, int D, bool SLAB>
-__global__ __launch_bounds__(256) void fa_bwd_kp_prep(const AttnBwdParams bp, float* __restrict__ rowc,
-                                                      float* __restrict__ acc) {
-  typedef typename Elem<T>::storage S;
-  const int N = bp.f.Nq, nqs = N / KP_BQ;
-  const int bh = blockIdx.x / nqs, s = blockIdx.x % nqs;
-  const int b = bh / bp.f.H, h = bh % bp.f.H;
-  const int tid = threadIdx.x, r = tid >> 2, k = tid & 3, row = s * KP_BQ + r;
-  const S* o = (const S*)bp.f.o + b * bp.f.o_sb + h * bp.f.o_sh + (int64_t)row * bp.f.o_sn;
-  const S* g = (const S*)bp.dout + b * bp.do_sb + h * bp.do_sh + (int64_t)row * bp.do_sn;
-  float dsum = 0.f;
-#pragma unroll
-  for (int c = k; c < D / 8; c += 4) {
-    const uint4 uo = *reinterpret_cast<const uint4*>(o + 8 * c);
-    const uint4 ug = *reinterpret_cast<const uint4*>(g + 8 * c);
-    const uint32_t wo[4] = {uo.x, uo.y, uo.z, uo.w}, wg[4] = {ug.x, ug.y, ug.z, ug.w};
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      dsum = fmaf(Elem<T>::to_f((S)(wo[w] & 0xffff)), Elem<T>::to_f((S)(wg[w] & 0xffff)), dsum);
-      dsum = fmaf(Elem<T>::to_f((S)(wo[w] >> 16)), Elem<T>::to_f((S)(wg[w] >> 16)), dsum);
-    }
-  }
-  dsum += __shfl_xor(dsum, 1, 64);
-  dsum += __shfl_xor(dsum, 2, 64);
-  float* rc = rowc + ((int64_t)bh * nqs + s) * 128;
-  if (k == 0) {
-    rc[row_perm(r)] = -bp.f.lse[(int64_t)bh * N + row] * kLog2e;
-    rc[64 + row_perm(r)] = -dsum;
-  }
-  if constexpr (!SLAB) {
-    float4* z = reinterpret_cast<float4*>(acc + ((int64_t)bh * N + s * KP_BQ) * D);
-    for (int i = tid; i < KP_BQ * D / 4; i += 256) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
+// ---- (1) row constants + zeroed dQ accumulator: fa_bwd_rowc_prep (fa_bwd_common.h), each thread
+// over the 16-B chunks k, k+4, ... of d ---------------------------------------------------------
 
 // ---- (2) main kernel ---------------------------------------------------------------------------
 template <typename T, int D, bool CAUSAL, bool ROPE, bool SLAB, int WV>
@@ -176,8 +128,7 @@ __global__ __launch_bounds__(64 * WV, 1) void fa_bwd_kp_kernel(const AttnBwdPara
 
   // ---- per-lane LDS offsets (row bases are multiples of 16 rows: the swizzle is the lane's) ----
   uint32_t roff[NKS];  // row fragments: row l32, chunk 2ks + hh
-#pragma unroll
-  for (int ks = 0; ks < NKS; ++ks) roff[ks] = (uint32_t)(l32 * RB + (((2 * ks + hh) ^ swz<RB>(l32)) << 4));
+  row_offsets<RB>(l32, hh, roff);
   uint32_t toa[NDT], tob[NDT];  // transposed fragments of d column tile dt (Q, dO, K images)
 #pragma unroll
   for (int dt = 0; dt < NDT; ++dt) tr_offsets<RB>(lane, dt, toa[dt], tob[dt]);
@@ -185,15 +136,7 @@ __global__ __launch_bounds__(64 * WV, 1) void fa_bwd_kp_kernel(const AttnBwdPara
 #pragma unroll
   for (int qq = 0; qq < 2; ++qq) tr_offsets<128>(lane, qq, dsa[qq], dsb[qq]);
   auto rowf = [&](const char* img, int ks) -> F { return as_frag<T>(*reinterpret_cast<const uint4*>(img + roff[ks])); };
-  auto trf2 = [&](const char* img, uint32_t oa, uint32_t ob) -> F {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + oa));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + ob));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(F, v);
-  };
+  auto trf2 = [&](const char* img, uint32_t oa, uint32_t ob) -> F { return lds_tr_read<T>(img, oa, ob); };
 
   // ---- LDS-DMA staging --------------------------------------------------------------------------
   TileDma<KP_BQ, RB, CREAL, 2> dq_, dd_;  // Q / dO slices (waves 0-3)
@@ -349,7 +292,9 @@ __global__ __launch_bounds__(64 * WV, 1) void fa_bwd_kp_kernel(const AttnBwdPara
         pf[g][1] = pack_acc<T>(sa[g], 1);
         sf[g][0] = pack_acc<T>(dp[g], 0);
         sf[g][1] = pack_acc<T>(dp[g], 1);
-        // dSᵀ rows (block-local key 32 (GPW w + g) + l32): query halves 16s2 + 4hh + 0..3 and + 8
+        // dSᵀ rows (block-local key 32 (GPW w + g) + l32): query halves 16s2 + 4hh + 0..3 and + 8 (the
+        // write of store_dst, fa_bwd_common.h, kept inline: through the helper the compiler scheduled the
+        // d 80 causal 8-wave kernels differently)
         char* drow = dsimg + (32 * (GPW * wave + g) + l32) * 128 + 8 * hh;
         const int swl = swz<128>(l32);
 #pragma unroll
@@ -407,6 +352,8 @@ __global__ __launch_bounds__(64 * WV, 1) void fa_bwd_kp_kernel(const AttnBwdPara
   flush_dq();
 
   // ---- dK (x scale), dV of this wave's keys: lane = key, registers = d 32dt + 8g4 + 4hh + 0..3 ----
+  // (store_dkdv of fa_bwd_common.h, kept inline: through the helper 24 of these kernels changed their
+  // register counts by 1-4 and their waits)
   const Rope rope{bp.f.rope_cos, bp.f.rope_sin, D / 2};
 #pragma unroll
   for (int g = 0; g < GPW; ++g) {
@@ -471,7 +418,7 @@ __global__ __launch_bounds__(256) void fa_bwd_kp_dq(const AttnBwdParams bp, cons
 template <typename T, int D, bool ROPE, bool SLAB>
 void launch_kp(const AttnBwdParams& bp, float* rowc, float* acc, hipStream_t s) {
   const int BH = bp.f.B * bp.f.H, N = bp.f.Nq;
-  hipLaunchKernelGGL((fa_bwd_kp_prep<T, D, SLAB>), dim3((unsigned)(BH * (N / KP_BQ))), dim3(256), 0, s, bp, rowc, acc);
+  hipLaunchKernelGGL((fa_bwd_rowc_prep<T, D, false, !SLAB>), dim3((unsigned)(BH * (N / KP_BQ))), dim3(256), 0, s, bp, rowc, acc);
   const dim3 grid((unsigned)(BH * kp_nkb(bp)));
   if (kp_waves(bp) == 8) {
     if (bp.f.causal) hipLaunchKernelGGL((fa_bwd_kp_kernel<T, D, true, ROPE, SLAB, 8>), grid, dim3(512), 0, s, bp, rowc, acc);

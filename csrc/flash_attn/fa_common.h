@@ -1,4 +1,6 @@
-// Shared building blocks of the CDNA4 FlashAttention-2 kernels (fa_fwd.hip, fa_bwd.hip).
+// Shared building blocks of the CDNA4 FlashAttention-2 kernels: the forward (fa_fwd.hip), the decode
+// kernel (fa_decode.hip) and every backward form (fa_bwd.hip; fa_bwd_fused.hip, fa_bwd_hs.hip and
+// fa_bwd_kp.hip, whose common pieces are in fa_bwd_common.h).
 //
 // MFMA shapes: 16-bit inputs use v_mfma_f32_32x32x16_{bf16,f16}; fp32 inputs use the exact
 // f32-in/f32-acc v_mfma_f32_32x32x2_f32 (no TF32-like shortcut exists on gfx950, and the
@@ -151,22 +153,55 @@ __device__ __forceinline__ typename Mma16<T>::frag lds_row_frag(const char* img,
 
 // Transposed fragment (A operand = image^T): lane (d = dt*32 + (lane&31), half h) gets the 8
 // elements image[row0 + 16s + 8(j>>2) + 4h + (j&3)][d], j = 0..7, via two ds_read_b64_tr_b16.
-template <typename T, int RB>
-__device__ __forceinline__ typename Mma16<T>::frag lds_tr_frag(const char* img, int row0, int s, int dt, int lane) {
+// lds_tr_addr: where the two reads go. P is the image pointer on the device and an integer on the
+// host (img = 0: byte offsets), so csrc/tests/host_checks.cpp checks the statement the kernels run.
+template <int RB, typename P>
+__host__ __device__ __forceinline__ void lds_tr_addr(P img, int row0, int s, int dt, int lane, P& pa, P& pb) {
   const int i = lane & 15, gq = (lane >> 4) & 1, h = lane >> 5;
   const int chunk = dt * 4 + gq * 2 + ((i & 3) >> 1);
   const int within = (i & 1) * 8;
   const int ra = row0 + 16 * s + 4 * h + (i >> 2);
   const int rb = ra + 8;
-  const lds_s16x4* pa = (const lds_s16x4*)(img + lds_off<RB>(ra, chunk) + within);
-  const lds_s16x4* pb = (const lds_s16x4*)(img + lds_off<RB>(rb, chunk) + within);
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)pa);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)pb);
+  pa = img + lds_off<RB>(ra, chunk) + within;
+  pb = img + lds_off<RB>(rb, chunk) + within;
+}
+// The same two offsets relative to a row base that is a multiple of 16 rows, for column tile c (32
+// elements) of an image with R-byte rows: every swizzle repeats after 16 rows, so these depend on the
+// lane only. The one-kernel backwards keep them per lane and put the base in the instruction's
+// immediate offset. host_checks.cpp proves base + tr_offsets == lds_tr_addr for every lane, tile and
+// base, and the reads bank-conflict free.
+template <int R>
+__host__ __device__ __forceinline__ void tr_offsets(int lane, int c, uint32_t& oa, uint32_t& ob) {
+  const int hh = lane >> 5, ti = lane & 15;
+  const int tra = 4 * hh + (ti >> 2), tcl = ((lane >> 4) & 1) * 2 + ((ti & 3) >> 1);
+  const int ch = (c << 2) | tcl;
+  oa = (uint32_t)(tra * R + ((ch ^ swz<R>(tra)) << 4) + (ti & 1) * 8);
+  ob = (uint32_t)((tra + 8) * R + ((ch ^ swz<R>(tra + 8)) << 4) + (ti & 1) * 8);
+}
+// one ds_read_b64_tr_b16, and the two reads' results as one fragment
+__device__ __forceinline__ s16x4 lds_tr16(const char* p) { return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p); }
+template <typename T>
+__device__ __forceinline__ typename Mma16<T>::frag tr_pack(s16x4 lo, s16x4 hi) {
   typedef __attribute__((ext_vector_type(8))) short s16x8;
   s16x8 v;
   v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
   v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
   return __builtin_bit_cast(typename Mma16<T>::frag, v);
+}
+// the read pair at img + oa / img + ob (offsets from tr_offsets + an immediate row base)
+template <typename T>
+__device__ __forceinline__ typename Mma16<T>::frag lds_tr_read(const char* img, uint32_t oa, uint32_t ob) {
+  const s16x4 lo = lds_tr16(img + oa);
+  const s16x4 hi = lds_tr16(img + ob);
+  return tr_pack<T>(lo, hi);
+}
+template <typename T, int RB>
+__device__ __forceinline__ typename Mma16<T>::frag lds_tr_frag(const char* img, int row0, int s, int dt, int lane) {
+  const char *pa, *pb;
+  lds_tr_addr<RB>(img, row0, s, dt, lane, pa, pb);
+  const s16x4 lo = lds_tr16(pa);
+  const s16x4 hi = lds_tr16(pb);
+  return tr_pack<T>(lo, hi);
 }
 
 // f32 images: 4 consecutive floats of row r starting at element e (e % 4 == 0)
@@ -354,7 +389,8 @@ __host__ __device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 
 
 // Staging position of query row r (0..63) of a backward tile so that lane-half h of 32-row group t
 // finds its 16 accumulator rows (acc_row(reg, h)) at 32t + 16h + reg: one 64-B read per lane loads
-// a row-constant accumulator (fa_bwd.hip dK/dV kernel).
+// a row-constant accumulator (-delta as dP's start, -lse·log2e: the fa_bwd.hip dK/dV kernel and the
+// one-kernel forms, whose prep kernel / in-kernel delta write this order, fa_bwd_common.h).
 __host__ __device__ __forceinline__ int row_perm(int r) {
   return (r & ~31) | (((r >> 2) & 1) << 4) | (((r >> 3) & 3) << 2) | (r & 3);
 }

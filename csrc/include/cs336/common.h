@@ -159,6 +159,13 @@ inline int stream_grid(int64_t work_items, int block) {
   return (int)g;
 }
 
+// Integer environment switch (host): dflt when the variable is unset or, unless empty_is_unset is
+// false, set to the empty string; else atoi of its value.
+inline int env_int(const char* name, int dflt, bool empty_is_unset = true) {
+  const char* e = getenv(name);
+  return e && (*e || !empty_is_unset) ? atoi(e) : dflt;
+}
+
 #define CS336_HIP_CHECK(expr)                                                     \
   do {                                                                            \
     hipError_t _e = (expr);                                                       \

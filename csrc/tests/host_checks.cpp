@@ -7,7 +7,9 @@
 //    (batch*head, tile level) BIJECTIVELY, for every head-group size the host can pick;
 //  * swz / lds_off: the XOR-swizzled LDS images keep every 16-B chunk of a row inside the row and
 //    the row-fragment (ds_read_b128) and transposed (ds_read_b64_tr_b16) reads bank-conflict free
-//    for every row width the kernels instantiate (64, 128, 192, 256 B);
+//    for every row width the kernels instantiate (64, 128, 192, 256 B; 128 is also the dSᵀ image),
+//    at the addresses the kernels compute: row_offsets (fa_bwd_common.h), tr_offsets and
+//    lds_tr_addr (fa_common.h), which must agree with lds_off and with each other;
 //  * stream_k_mode / macro_tile_area (tensile_names.h): the Tensile name parsing behind the
 //    concurrency-safe GEMM selection.
 #include <cstdio>
@@ -15,7 +17,7 @@
 #include <vector>
 
 #include "cs336/tensile_names.h"
-#include "fa_common.h"
+#include "fa_bwd_common.h"
 
 using namespace cs336;
 using namespace cs336::fa;
@@ -73,42 +75,49 @@ static void check_swizzle() {
     }
     CHECK((int)phys.size() == CPR, "RB=%d row %d: swizzle is not a permutation", RB, r);
   }
-  // ds_read_b128 row fragments: 4 groups of 16 lanes, lane -> row r0 + (lane & 31), chunk 2ks + (lane >> 5)
+  // ds_read_b128 row fragments: 4 groups of 16 lanes, lane -> row r0 + (lane & 31), chunk 2ks + (lane >> 5),
+  // addressed as the one-kernel backwards do: a 32-row base + row_offsets (which must equal lds_off)
   const int g128[2][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
                            {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31}};
+  constexpr int NKS = CPR / 2;
   int worst = 0;
   for (int r0 = 0; r0 < 128; r0 += 32)
-    for (int ks = 0; 2 * ks + 1 < CPR; ++ks)
+    for (int ks = 0; ks < NKS; ++ks)
       for (int hi = 0; hi < 2; ++hi)
         for (const auto& g : g128) {
           int banks[64] = {0};
           for (int l : g) {
             const int lane = l + 32 * hi;
-            const int a = lds_off<RB>(r0 + (lane & 31), 2 * ks + (lane >> 5));
+            uint32_t roff[NKS];
+            row_offsets<RB>(lane & 31, lane >> 5, roff);
+            const int a = r0 * RB + (int)roff[ks];
+            CHECK(a == lds_off<RB>(r0 + (lane & 31), 2 * ks + (lane >> 5)), "RB=%d row_offsets lane %d ks %d base %d", RB, lane, ks, r0);
             for (int w = 0; w < 4; ++w) ++banks[(a / 4 + w) % 64];
           }
           for (int b : banks) worst = b > worst ? b : worst;
         }
   CHECK(worst <= 1, "RB=%d ds_read_b128 row fragments: %d-way bank conflict", RB, worst);
-  // ds_read_b64_tr_b16 (lds_tr_frag): one instruction = 32 lanes, rows row0+16s+4h+(i>>2) (+8 for the
-  // second read), chunk dt*4 + gq*2 + ((i&3)>>1), 8 B at (i&1)*8
+  // ds_read_b64_tr_b16: one instruction = one 32-lane half; the addresses are a 16-row base +
+  // tr_offsets (the one-kernel backwards), which must equal lds_tr_frag's own (lds_tr_addr) for
+  // every lane, column tile and base
   int worst_tr = 0;
-  const int ndt = RB / 64;  // 32-wide d tiles
-  for (int row0 = 0; row0 < 128; row0 += 32)
-    for (int s = 0; s < 2; ++s)
-      for (int dt = 0; dt < ndt; ++dt)
-        for (int h = 0; h < 2; ++h)
-          for (int second = 0; second < 2; ++second) {
-            int banks[64] = {0};
-            for (int lane = 32 * h; lane < 32 * h + 32; ++lane) {
-              const int i = lane & 15, gq = (lane >> 4) & 1;
-              const int c = dt * 4 + gq * 2 + ((i & 3) >> 1);
-              const int r = row0 + 16 * s + 4 * h + (i >> 2) + 8 * second;
-              const int a = lds_off<RB>(r, c) + (i & 1) * 8;
-              for (int w = 0; w < 2; ++w) ++banks[(a / 4 + w) % 64];
-            }
-            for (int b : banks) worst_tr = b > worst_tr ? b : worst_tr;
+  const int ndt = RB / 64;  // 32-wide column tiles
+  for (int base = 0; base < 256; base += 16)
+    for (int dt = 0; dt < ndt; ++dt)
+      for (int h = 0; h < 2; ++h)
+        for (int second = 0; second < 2; ++second) {
+          int banks[64] = {0};
+          for (int lane = 32 * h; lane < 32 * h + 32; ++lane) {
+            uint32_t oa, ob;
+            tr_offsets<RB>(lane, dt, oa, ob);
+            int fa, fb;
+            lds_tr_addr<RB>(0, base & ~31, (base >> 4) & 1, dt, lane, fa, fb);
+            CHECK(base * RB + (int)oa == fa && base * RB + (int)ob == fb, "RB=%d tr_offsets lane %d tile %d base %d", RB, lane, dt, base);
+            const int a = base * RB + (int)(second ? ob : oa);
+            for (int w = 0; w < 2; ++w) ++banks[(a / 4 + w) % 64];
           }
+          for (int b : banks) worst_tr = b > worst_tr ? b : worst_tr;
+        }
   CHECK(worst_tr <= 1, "RB=%d ds_read_b64_tr_b16: %d-way bank conflict", RB, worst_tr);
   std::printf("swizzle RB=%d: row-fragment reads %d-way, transposed reads %d-way\n", RB, worst, worst_tr);
 }
@@ -123,7 +132,7 @@ static void check_names() {
   CHECK(macro_tile_area("Cijk_noMT") == 0 && macro_tile_area("_MTx") == 0, "no MT");
 }
 
-// the dK/dV kernel's row-constant staging: row_perm is a bijection on each 64-row tile that puts
+// the row-constant staging of the backward kernels: row_perm is a bijection on each 64-row tile that puts
 // accumulator register reg of lane-half h (32-row group t) at 32t + 16h + reg, and the LDS-DMA
 // source chunks land the same rows in the same places
 static void check_row_perm() {

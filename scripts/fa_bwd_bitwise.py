@@ -1,7 +1,9 @@
 """Dump (or compare) the HIP FA backward's dq/dk/dv on fixed inputs, to check two builds bitwise:
     CS336_LIB=.../variants/base/libcs336_hip.so python scripts/fa_bwd_bitwise.py dump /tmp/a.pt
     python scripts/fa_bwd_bitwise.py check /tmp/a.pt
-Shapes: the low-parallelism (split) regime, with and without the mask, RoPE and positions."""
+Shapes: the low-parallelism (split) regime, with and without the mask, RoPE and positions, and small
+shapes each one-kernel form accepts: run with CS336_FA_BWD=3 (head-sequential), 1 (fused) or
+2 with CS336_FA_KP_SLAB=1 (key-block parallel; its atomic form is not reproducible run to run)."""
 
 import os
 import sys
@@ -14,6 +16,9 @@ from cs336_systems.models import RotaryEmbedding
 from cs336_systems.ops._ext import ops as hip_ops
 
 SHAPES = [(1, 1, 256, 32), (1, 1, 512, 16), (1, 1, 2048, 64), (1, 1, 4096, 128), (2, 3, 1000, 64), (1, 2, 2048, 80)]
+SHAPES += [(2, 3, 128, 64), (1, 2, 256, 64), (1, 1, 1152, 64)]  # head-sequential (N % 128 == 0; 1152: prep-kernel delta)
+SHAPES += [(1, 2, 192, 64), (1, 1, 1024, 64)]  # fused (N % 64 == 0, N <= 1024)
+SHAPES += [(1, 2, 320, 64), (1, 2, 256, 80)]  # key-block parallel (a partial last key block; d 80)
 
 
 def run():

@@ -11,15 +11,19 @@ timeout -s KILL 90 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAI
 timeout -s KILL 90 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_VMEM SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_MISC --output-format csv -d gpurun_out/pmc_$TAG/p2 -o run -- python scripts/fa_bwd_one.py $SHAPE > /dev/null 2>&1 || exit 1
 timeout -s KILL 90 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/pmc_$TAG/kt -o run -- python scripts/fa_bwd_one.py $SHAPE > /dev/null 2>&1 || exit 1
 python - "$TAG" <<'P'
-import csv, glob, json, statistics, sys
+import csv, glob, json, re, statistics, sys
 tag = sys.argv[1]
 res = {}
 
 
 def kind(n):
-    for key, name in (("kp", "fa_bwd_kp_kernel"), ("kp_prep", "fa_bwd_kp_prep"), ("kp_dq", "fa_bwd_kp_dq"),
+    # the shared prep kernel fa_bwd_rowc_prep<T, D, CONTIG, ZERO_ACC>: CONTIG is the hs chunk order
+    m = re.search(r"fa_bwd_rowc_prep(?:<.*?(true|false), (?:true|false)>)?", n)
+    if m:
+        return {"true": "hs_prep", "false": "kp_prep", None: "rowc_prep"}[m.group(1)]
+    for key, name in (("kp", "fa_bwd_kp_kernel"), ("kp_dq", "fa_bwd_kp_dq"),
                       ("dq", "fa_bwd_dq"), ("dkdv", "fa_bwd_dkdv"), ("fused", "fa_bwd_fused"),
-                      ("hs", "fa_bwd_hs_kernel"), ("hs_prep", "fa_bwd_hs_prep")):
+                      ("hs", "fa_bwd_hs_kernel")):
         if name in n:
             return key
     return None
