@@ -1,4 +1,5 @@
 from .configs import DEFAULT_THETA, DEFAULT_VOCAB, MODEL_CONFIGS, get_model_config, param_count, train_flops_per_token
+from .decode_graph import DecodeGraph
 from .kv_cache import KVCache
 from .transformer import (
     BasicsTransformerLM,
@@ -28,6 +29,7 @@ def build_model(size: str, context_length: int, vocab_size: int = DEFAULT_VOCAB,
 __all__ = [
     "BasicsTransformerLM",
     "CausalMultiHeadSelfAttention",
+    "DecodeGraph",
     "Embedding",
     "KVCache",
     "Linear",

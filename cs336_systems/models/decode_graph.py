@@ -1,0 +1,92 @@
+"""One cached decode step of ``BasicsTransformerLM``, captured into a HIP graph and replayed.
+
+An eager decode step is host-bound: Python issues about 190 GEMMs and 290 other launches per token
+for roughly a millisecond of GPU work (``profiles/decode_attention.md``). Nothing in the step
+synchronizes the host -- positions and lengths live in the device tensor ``cache.lengths`` -- so the
+whole step is recorded once into a ``torch.cuda.CUDAGraph`` (hipGraph on ROCm) and replayed with one
+launch per token. Its M = batch projections run the weight-streaming skinny-M kernel
+(``csrc/gemm/gemm_skinny.hip``) through ``gemm.skinny_decode()``.
+
+One step function serves both modes: the decode branch of ``forward_cached`` with the FIXED
+decode-attention bound ``max_kv_len = cache.max_len`` (the key-split count is baked into a captured
+launch and cannot follow the host's ``start + 1``). ``capture=False`` runs it eagerly on every
+:meth:`DecodeGraph.step`: the fallback, the CPU path and the comparison arm of the tests
+(``tests/test_decode_graph_gpu.py`` checks replays bitwise against it).
+
+Contract: the graph is tied to this ``cache`` object and to the parameters' storage.
+``cache.reset()`` followed by a new eager prefill of any length and then ``step`` is supported, and
+in-place weight updates are picked up by the next replay; ``model.to(...)`` or anything else that
+re-allocates the parameters invalidates the graph (not detected). An fp32 model under autocast works
+(construct and step under the same autocast context: the weight casts are captured) but re-casts
+every weight per token -- hold the model in bf16.
+"""
+
+from __future__ import annotations
+
+import torch
+
+from ..ops import gemm
+
+
+class DecodeGraph:
+    """``logits = dg.step(tok)``: ``tok`` (B, 1) int64 -> (B, 1, vocab), the cache advanced by one."""
+
+    def __init__(self, model, cache, capture: bool = True, warmup: int = 2):
+        if getattr(model, "tensor_parallel", None) is not None or any(
+                layer.attn.context_parallel is not None for layer in model.layers):
+            raise NotImplementedError("DecodeGraph does not support tensor / context parallelism")
+        if cache.num_layers != len(model.layers):
+            raise ValueError("cache was built for a different number of layers")
+        if capture and not cache.k.is_cuda:
+            raise ValueError("DecodeGraph(capture=True) captures HIP graphs: the model and cache must be on a GPU")
+        self.model, self.cache = model, cache
+        self.graph = None
+        if not capture:
+            return
+        dev = cache.k.device
+        self.tok = torch.zeros(cache.batch, 1, dtype=torch.int64, device=dev)
+        # Warm-up and capture leave the cache as they found it: a warm-up step writes its K / V rows
+        # at index ``length``, which no one reads (on a full cache the append kernel stores nothing),
+        # and lengths / length are put back; capturing executes nothing but the host bookkeeping.
+        lengths, length = cache.lengths.clone(), cache.length
+        self.stream = torch.cuda.Stream(device=dev)
+        self.stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(self.stream):
+            # eager steps on the capture stream: allocator pools, lazy initialisation and GEMM
+            # selection, none of which may happen inside a capture
+            for _ in range(max(1, warmup)):
+                self._run(self.tok)
+                cache.lengths.copy_(lengths)
+                cache.length = length
+        torch.cuda.current_stream(dev).wait_stream(self.stream)
+        torch.cuda.synchronize(dev)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=self.stream):
+            self.logits = self._run(self.tok)
+        cache.length = length
+
+    @torch.no_grad()
+    def _run(self, tok: torch.Tensor) -> torch.Tensor:
+        """The step both modes run: the decode branch of ``forward_cached`` (also on an empty cache,
+        where the warm-up's row lands at index 0, unread) with the fixed attention bound."""
+        with gemm.skinny_decode():
+            return self.model._forward_cached(tok, self.cache, max(self.cache.length, 1), self.cache.max_len)
+
+    def step(self, tok: torch.Tensor) -> torch.Tensor:
+        """Logits (B, 1, vocab) of the token ``tok`` (B, 1) that follows the cached ones; the cache
+        then holds it too. With ``capture=True`` the result is the graph's static output buffer: it
+        stays valid until the next ``step``, which overwrites it. A failed check changes nothing."""
+        cache = self.cache
+        if tok.dim() != 2 or tok.shape[0] != cache.batch or tok.shape[1] != 1:
+            raise ValueError(f"DecodeGraph.step takes (B, 1) token ids with B = {cache.batch}")
+        if cache.length < 1:
+            raise ValueError("DecodeGraph.step on an empty cache: prefill first (forward_cached on the prompt)")
+        if cache.length >= min(cache.max_len, self.model.context_length):
+            raise ValueError(f"{cache.length} cached + 1 new token exceed the cache (max_len {cache.max_len}, "
+                             f"context_length {self.model.context_length})")
+        if self.graph is None:
+            return self._run(tok)
+        self.tok.copy_(tok)
+        self.graph.replay()
+        cache.length += 1  # the captured ``lengths += 1`` advanced the device tensor
+        return self.logits

@@ -371,12 +371,14 @@ class CausalMultiHeadSelfAttention(nn.Module):
         with annotate("out_proj"):
             return self.output_proj(o)
 
-    def forward_cached(self, x3, k_cache, v_cache, start: int, pos=None, kv_len=None) -> torch.Tensor:
+    def forward_cached(self, x3, k_cache, v_cache, start: int, pos=None, kv_len=None, max_kv_len=None) -> torch.Tensor:
         """Attention of ``forward_cached`` (inference only). ``x3`` (B, n, d_model); ``k_cache`` /
         ``v_cache`` this layer's (B, H, max_len, dk) cache views. ``start == 0``: prefill -- the
         ordinary causal attention over the n tokens at positions 0..n-1, whose rotated K and V are
         copied into cache rows [0, n). Otherwise one decode step (n == 1): ``pos`` (B,) int32 is the
-        new token's slot and RoPE position, ``kv_len = pos + 1`` its key count."""
+        new token's slot and RoPE position, ``kv_len = pos + 1`` its key count. ``max_kv_len``: the
+        host-side bound of ``kv_len`` that picks the decode kernel's split count (default
+        ``start + 1``; a captured step passes a fixed one)."""
         B, n, _ = x3.shape
         H, dk = self.num_heads, self.d_k
         w = [self.q_proj.weight, self.k_proj.weight, self.v_proj.weight]
@@ -392,7 +394,8 @@ class CausalMultiHeadSelfAttention(nn.Module):
                 q = ops.kv_append_rope(qkv.view(B, 3 * H * dk), self.positional_encoder.cos, self.positional_encoder.sin,
                                        pos, k_cache, v_cache)
             with annotate("decode_attention"):
-                o, _ = ops.decode_attention(q, k_cache, v_cache, kv_len, max_kv_len=start + 1)
+                o, _ = ops.decode_attention(q, k_cache, v_cache, kv_len,
+                                            max_kv_len=start + 1 if max_kv_len is None else max_kv_len)
             o = o.reshape(B, 1, H * dk)
         else:
             q, k, v = (qkv.view(B, n, 3, H, dk)[:, :, i].transpose(1, 2) for i in range(3))
@@ -623,6 +626,15 @@ class BasicsTransformerLM(nn.Module):
         if start + n > min(cache.max_len, self.context_length):
             raise ValueError(f"{start} cached + {n} new tokens exceed the cache (max_len {cache.max_len}, "
                              f"context_length {self.context_length})")
+        return self._forward_cached(x, cache, start)
+
+    def _forward_cached(self, x: torch.Tensor, cache, start: int, max_kv_len: int | None = None) -> torch.Tensor:
+        """The body of :meth:`forward_cached` after its checks: the prefill (``start == 0``) or one
+        decode step (``start > 0``) over the layers, the cache advanced by the tokens of ``x``.
+        ``max_kv_len``: see ``CausalMultiHeadSelfAttention.forward_cached``. Nothing here reads the
+        host mirror ``cache.length`` or synchronizes the host, so a decode step can be captured into
+        a HIP graph (``models/decode_graph.py``)."""
+        n = x.shape[1]
         pos = kv_len = None
         if start > 0:  # once per step, shared by all layers
             pos = cache.lengths
@@ -634,7 +646,7 @@ class BasicsTransformerLM(nn.Module):
             y = self.layers[0].ln1(h)
             for i, layer in enumerate(self.layers):
                 with annotate(f"layer{i}"):
-                    a = layer.attn.forward_cached(y, cache.k[i], cache.v[i], start, pos, kv_len)
+                    a = layer.attn.forward_cached(y, cache.k[i], cache.v[i], start, pos, kv_len, max_kv_len)
                     self._reading(layer.ln2)
                     h, y = ops.add_rmsnorm(h, a, layer.ln2.weight, layer.ln2.eps)
                     f = layer.ffn(y)
@@ -644,7 +656,8 @@ class BasicsTransformerLM(nn.Module):
         else:
             for i, layer in enumerate(self.layers):
                 with annotate(f"layer{i}"):
-                    h = h + layer.attn.forward_cached(layer.ln1(h), cache.k[i], cache.v[i], start, pos, kv_len)
+                    h = h + layer.attn.forward_cached(layer.ln1(h), cache.k[i], cache.v[i], start, pos, kv_len,
+                                                      max_kv_len)
                     h = h + layer.ffn(layer.ln2(h))
             y = self.ln_final(h)
         cache.advance(n)
@@ -660,6 +673,7 @@ class BasicsTransformerLM(nn.Module):
         top_k: int | None = None,
         eos_token_id: int | None = None,
         use_cache: bool = False,
+        graph=False,
     ) -> torch.Tensor:
         """Autoregressive sampling (``model.py:255-310``) with a working top-k filter (the
         reference's ``masked_fill`` is not in place and its threshold broadcast is wrong for B>1).
@@ -667,24 +681,51 @@ class BasicsTransformerLM(nn.Module):
         ``use_cache=True``: prefill a KV cache on the prompt (its last ``context_length`` tokens),
         then one :meth:`forward_cached` step per token while the sequence fits the window; once the
         window is full the remaining tokens take the uncached sliding-window step (a window that
-        slides re-positions every key, which only a full recomputation defines)."""
+        slides re-positions every key, which only a full recomputation defines).
+
+        ``graph=True`` (GPU models, with ``use_cache=True``): after the prefill the cached step is
+        captured into a HIP graph over the skinny-M GEMM kernel (:class:`DecodeGraph`) and every
+        cached step is one replay. ``graph=<DecodeGraph>`` reuses a caller-owned graph of this model
+        and batch size (its cache is reset and prefilled), which saves the capture per call.
+        Sampling stays eager."""
+        from .decode_graph import DecodeGraph
+
         if x.dim() == 1:
             x = x.unsqueeze(0)
         orig = x.size(-1)
-        cache = None
+        cache = dg = None
+        if graph is not False and graph is not None:
+            if not use_cache:
+                raise ValueError("generate(graph=...) needs use_cache=True")
+            if isinstance(graph, DecodeGraph):
+                if graph.model is not self:
+                    raise ValueError("the DecodeGraph belongs to a different model")
+                if graph.cache.batch != x.size(0):
+                    raise ValueError(f"batch {x.size(0)} does not match the DecodeGraph's {graph.cache.batch}")
+                dg = graph
+            elif graph is not True:
+                raise ValueError("graph must be a bool or a DecodeGraph")
+            elif not self.lm_head.weight.is_cuda:
+                raise ValueError("generate(graph=True) captures a HIP graph: the model must be on a GPU")
         if use_cache and max_new_tokens > 0:
             from .kv_cache import KVCache
 
-            w = self.lm_head.weight
-            dev = w.device.type
-            cdt = torch.get_autocast_dtype(dev) if torch.is_autocast_enabled(dev) else w.dtype
-            cache = KVCache(self, x.size(0), device=w.device, dtype=cdt)
+            if dg is not None:
+                cache = dg.cache
+                cache.reset()
+            else:
+                w = self.lm_head.weight
+                dev = w.device.type
+                cdt = torch.get_autocast_dtype(dev) if torch.is_autocast_enabled(dev) else w.dtype
+                cache = KVCache(self, x.size(0), device=w.device, dtype=cdt)
         for _ in range(max_new_tokens):
             ctx = x[:, -self.context_length :] if x.size(1) > self.context_length else x
             if cache is not None and cache.length == 0:
                 logits = self.forward_cached(ctx, cache)  # prefill
             elif cache is not None and cache.length + 1 == x.size(1) <= self.context_length:
-                logits = self.forward_cached(x[:, -1:], cache)
+                if graph is True and dg is None:
+                    dg = DecodeGraph(self, cache, capture=True)
+                logits = dg.step(x[:, -1:]) if dg is not None else self.forward_cached(x[:, -1:], cache)
             else:
                 cache = None  # the window is full (and slides from here on): full recomputation
                 logits = self.forward(ctx)

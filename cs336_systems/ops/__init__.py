@@ -14,6 +14,7 @@ from .flash_attention import (
 )
 from .rmsnorm import add_rmsnorm, add_rmsnorm_ref, rmsnorm, rmsnorm_ref
 from .rope import rope, rope_ref
+from .skinny import skinny_linear, skinny_linear_ref
 from .swiglu import silu, silu_mul, silu_mul_ref
 
 __all__ = [
@@ -44,6 +45,8 @@ __all__ = [
     "rmsnorm_ref",
     "rope",
     "rope_ref",
+    "skinny_linear",
+    "skinny_linear_ref",
     "silu",
     "silu_mul",
     "silu_mul_ref",

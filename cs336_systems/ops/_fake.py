@@ -170,3 +170,10 @@ if hasattr(torch.ops.cs336, "fa_decode"):  # (absent from libraries built before
     def _kv_append_rope(qkv, cos, sin, pos, k_cache, v_cache):
         B, H, _, D = k_cache.shape
         return qkv.new_empty((B, H, D))
+
+
+if hasattr(torch.ops.cs336, "gemm_skinny"):  # (absent from libraries built before the decode graph: A/B baselines)
+
+    @register_fake("cs336::gemm_skinny")
+    def _gemm_skinny(x, w, out):
+        return None

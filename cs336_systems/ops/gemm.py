@@ -33,6 +33,7 @@ chip can deadlock (``csrc/blas/lt_gemm.cpp``, ``profiles/r2_streamk_hang.md``).
 from __future__ import annotations
 
 import os
+from contextlib import contextmanager
 
 import torch
 
@@ -290,8 +291,61 @@ def gemm8_rope(x: torch.Tensor, w: torch.Tensor, cos: torch.Tensor, sin: torch.T
     return out
 
 
+SKINNY_MAX_M = 16  # rows the skinny-M kernel takes (one MFMA tile of batch rows)
+_SKINNY = False
+
+
+@contextmanager
+def skinny_decode():
+    """While active, :func:`mm_nt` sends calls with at most ``SKINNY_MAX_M`` rows that
+    :func:`skinny_ok` takes to the weight-streaming kernel (``csrc/gemm/gemm_skinny.hip``): the
+    M = batch projections of a decode step. Off by default; outside it ``mm_nt`` is unchanged."""
+    global _SKINNY
+    prev, _SKINNY = _SKINNY, True
+    try:
+        yield
+    finally:
+        _SKINNY = prev
+
+
+def skinny_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
+    """Whether ``cs336::gemm_skinny`` takes ``x @ w.T``: GPU bf16 / fp16 of one dtype, at most 16
+    rows, K % 8 == 0, row-major operands with 16-B aligned rows (``w`` rows at least K apart)."""
+    return (
+        x.is_cuda
+        and w.is_cuda
+        and x.dtype in (torch.bfloat16, torch.float16)
+        and w.dtype == x.dtype
+        and x.dim() == 2
+        and w.dim() == 2
+        and x.shape[1] == w.shape[1]
+        and _aligned_rows(x)
+        and _aligned_rows(w)
+        and x.stride(0) >= 0
+        and (w.shape[0] == 1 or w.stride(0) >= w.shape[1])
+        and ext_available()
+        and ops().gemm_skinny_ok(x.shape[0], w.shape[0], x.shape[1], x.element_size())
+    )
+
+
+def skinny_routed(m: int, n: int, k: int) -> bool:
+    """Shapes :func:`mm_nt` routes to the kernel inside :func:`skinny_decode`: all but long-K, short-N
+    weights of more than 16 Mi elements above 8 rows (the 2.7b W2, 2560 x 10240, at M 16: 27.6 us
+    against ``torch.mm``'s 26.0, ``profiles/decode_graph.md``; every other measured projection wins)."""
+    return not (m > 8 and k >= 4 * n and n * k > 1 << 24)
+
+
+def skinny_mm(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    out = torch.empty(x.shape[0], w.shape[0], device=x.device, dtype=x.dtype)
+    ops().gemm_skinny(x, w, out)
+    return out
+
+
 def mm_nt(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """``x @ w.T`` (forward of a linear layer; the input gradient through a Wᵀ shadow)."""
+    if (_SKINNY and x.shape[0] <= SKINNY_MAX_M and skinny_routed(x.shape[0], w.shape[0], x.shape[1])
+            and skinny_ok(x, w)):
+        return skinny_mm(x, w)
     mode = _mode()
     if mode == "blas":
         return torch.mm(x, w.t())

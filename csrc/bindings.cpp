@@ -1465,7 +1465,50 @@ at::Tensor kv_append_rope(const at::Tensor& qkv, const at::Tensor& cos, const at
   return q_out;
 }
 
+// ------------------------------------------------------------------------------------------
+// Skinny-M GEMM for decode (csrc/gemm/gemm_skinny.hip): out[M,N] = x[M,K] · w[N,K]ᵀ, M <= 16
+// ------------------------------------------------------------------------------------------
+bool gemm_skinny_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
+  return cs336::gemm_skinny_ok(M, N, K, elem_size);
+}
+
+void gemm_skinny(const at::Tensor& x, const at::Tensor& w, at::Tensor& out) {
+  check_cuda(x, "x");
+  check_cuda(w, "w");
+  check_cuda(out, "out");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2, "cs336: gemm_skinny takes x (M, K), w (N, K), out (M, N)");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf, "cs336: gemm_skinny takes bf16 / fp16");
+  TORCH_CHECK(w.scalar_type() == x.scalar_type() && out.scalar_type() == x.scalar_type(),
+              "cs336: gemm_skinny x / w / out dtype mismatch");
+  TORCH_CHECK(w.device() == x.device() && out.device() == x.device(), "cs336: gemm_skinny tensors must be on one device");
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(w.size(1) == K && out.size(0) == M && out.size(1) == N, "cs336: gemm_skinny shape mismatch");
+  TORCH_CHECK(M >= 1 && M <= 16, "cs336: gemm_skinny takes 1 <= M <= 16 (got ", M, ")");
+  TORCH_CHECK(K >= 8 && K % 8 == 0, "cs336: gemm_skinny needs K % 8 == 0 (got ", K, ")");
+  TORCH_CHECK(cs336::gemm_skinny_ok(M, N, K, x.element_size()), "cs336: gemm_skinny extents exceed the kernel's 32-bit row / k indices");
+  TORCH_CHECK(x.stride(1) == 1 && w.stride(1) == 1 && out.stride(1) == 1, "cs336: gemm_skinny operands must have a contiguous last dim");
+  TORCH_CHECK(x.stride(0) % 8 == 0 && (M == 1 || x.stride(0) >= 0), "cs336: gemm_skinny x row stride must be a non-negative multiple of 8");
+  TORCH_CHECK(w.stride(0) % 8 == 0 && (N == 1 || w.stride(0) >= K), "cs336: gemm_skinny w row stride must be a multiple of 8, at least K");
+  TORCH_CHECK(M == 1 || out.stride(0) >= N, "cs336: gemm_skinny out rows must not overlap");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(x.data_ptr()) % 16) == 0 && (reinterpret_cast<uintptr_t>(w.data_ptr()) % 16) == 0,
+              "cs336: gemm_skinny x and w must be 16-byte aligned");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(out.data_ptr()) % 2) == 0, "cs336: gemm_skinny out must be element aligned");
+  c10::DeviceGuard g(x.device());
+  cs336::SkinnyParams p;
+  p.x = x.data_ptr();
+  p.w = w.data_ptr();
+  p.out = out.data_ptr();
+  p.ldx = M == 1 ? 0 : x.stride(0);
+  p.ldw = N == 1 ? 0 : w.stride(0);
+  p.ldo = M == 1 ? 0 : out.stride(0);
+  p.M = (int)M; p.N = (int)N; p.K = (int)K;
+  p.vec_out = (reinterpret_cast<uintptr_t>(out.data_ptr()) % 8) == 0 && p.ldo % 4 == 0;
+  cs336::gemm_skinny(p, to_dtype(x), stream());
+}
+
 TORCH_LIBRARY(cs336, m) {
+  m.def("gemm_skinny(Tensor x, Tensor w, Tensor(a!) out) -> ()");
+  m.def("gemm_skinny_ok(int M, int N, int K, int elem_size) -> bool", &gemm_skinny_ok);
   m.def(
       "fa_decode(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_len, float scale, int max_kv_len, int splits=0) "
       "-> (Tensor o, Tensor lse)");
@@ -1534,6 +1577,7 @@ TORCH_LIBRARY(cs336, m) {
 }
 
 TORCH_LIBRARY_IMPL(cs336, CUDA, m) {
+  m.impl("gemm_skinny", &gemm_skinny);
   m.impl("fa_decode", &fa_decode);
   m.impl("kv_append_rope", &kv_append_rope);
   m.impl("fa_fwd", &fa_fwd);

@@ -262,4 +262,20 @@ struct AppendParams {
 };
 void kv_append_rope(const AppendParams& p, DType t, hipStream_t s);
 
+// ---- skinny-M GEMM for decode (csrc/gemm/gemm_skinny.hip) ----
+// out[M,N] = x[M,K] · w[N,K]ᵀ, 1 <= M <= 16, bf16 / fp16 with fp32 accumulation. Row strides in
+// elements; x / w rows 16-B aligned, K % 8 == 0, any N >= 1. Rows >= M, W rows >= N are never read.
+struct SkinnyParams {
+  const void* x;
+  const void* w;
+  void* out;
+  int64_t ldx, ldw, ldo;
+  int M, N, K;
+  bool vec_out;  // out rows 8-B aligned: 4 columns per store
+};
+bool gemm_skinny_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size);
+// W tiles per wave (1 / 2 / 4) and waves (K ranges) per workgroup the launch uses for (N, K)
+void gemm_skinny_plan(int N, int K, int& tn, int& waves);
+void gemm_skinny(const SkinnyParams& p, DType t, hipStream_t s);
+
 }  // namespace cs336
