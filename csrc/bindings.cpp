@@ -1214,12 +1214,19 @@ void gemm8(const at::Tensor& a, const at::Tensor& b, at::Tensor& c, int64_t epi,
 
 // diagnostic stamp buffer of gemm8 (CS336_G8_STAMP builds, scripts/gemm8_stamps.py): uint64 (blocks, 8)
 // or None = off; returns whether this build writes stamps
+// gemm8w writes 4 such rows per workgroup into the same buffer (scripts/gemm8w_stamps.py)
+uint64_t* g_stamp_buf = nullptr;
+int64_t g_stamp_rows = 0;
 bool gemm8_stamps(const std::optional<at::Tensor>& buf) {
+  g_stamp_buf = nullptr;
+  g_stamp_rows = 0;
   if (!buf.has_value()) return cs336::gemm8::set_stamp_buffer(nullptr, 0);
   const at::Tensor& b = *buf;
   TORCH_CHECK(b.is_cuda() && b.scalar_type() == at::kLong && b.is_contiguous() && b.dim() == 2 && b.size(1) == 8,
               "cs336: gemm8 stamp buffer must be a contiguous int64 (blocks, 8) GPU tensor");
-  return cs336::gemm8::set_stamp_buffer(reinterpret_cast<uint64_t*>(b.data_ptr<int64_t>()), b.size(0));
+  g_stamp_buf = reinterpret_cast<uint64_t*>(b.data_ptr<int64_t>());
+  g_stamp_rows = b.size(0);
+  return cs336::gemm8::set_stamp_buffer(g_stamp_buf, g_stamp_rows);
 }
 
 // QKV projection forward with RoPE in the store (gemm8 epi 3): c = a @ b.T with columns < rope_cols
@@ -1323,6 +1330,8 @@ void gemm8w(const at::Tensor& a, const at::Tensor& b, at::Tensor& out, int64_t s
     p.splits = (int)splits;
     p.trans_out = trans_out ? 1 : 0;
     p.accumulate = (accumulate || k0 > 0) ? 1 : 0;
+    p.stamps = g_stamp_buf;
+    p.stamp_rows = g_stamp_rows;
     TORCH_CHECK(cs336::gemm8::launch_w(p, (int)fn, stream()), "cs336: gemm8w does not take M=", M, " N=", N,
                 " K=", kc, " splits=", splits);
   }

@@ -56,6 +56,14 @@ struct WArgs {
   int M, N, K;
   int splits;
   int trans_out, accumulate;
+  // diagnostic builds only (-DCS336_G8_STAMP, scripts/gemm8w_stamps.py): the buffer of
+  // set_stamp_buffer, 4 rows of 8 uint64 per workgroup (split-major) -- per wave group the cycles of
+  // each of the four phases, summed over a few k-tiles in the middle of the range: reads + DMA issue
+  // + counted waits, the wait at the barrier before the MFMA cluster, from there to the next barrier;
+  // then the number of stamped k-tiles, the k-tiles, HW_ID, XCC_ID. Ignored by the shipped build,
+  // and by a launch whose workgroups need more than stamp_rows rows.
+  uint64_t* stamps = nullptr;
+  int64_t stamp_rows = 0;
 };
 bool launch_w(const WArgs& p, int fn, hipStream_t s);
 

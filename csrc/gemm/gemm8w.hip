@@ -8,20 +8,39 @@
 // (or the transposed roles, C stored transposed, when that tiles the shape better). Both operands are
 // "MN-major": the contraction index t is the row of the stored matrix. Structure follows gemm8
 // (csrc/gemm/gemm8.hip: 256 × 64·FN tile, BK 64, 8 waves 2 × 4, second wave group one barrier
-// behind, two LDS-DMA stages, one counted vmcnt per K-tile), with what MN-major operands change:
+// behind, two LDS-DMA stages, counted vmcnt waits), with what MN-major operands change:
 //
 // * LDS images are [64 t][R] (R = 256 or 320 columns, rows of 512 / 640 B) and every 16x16x32
 //   fragment is two ds_read_b64_tr_b16 (the transposed LDS read: lane i of a 16-lane group gets
 //   column i of 4 rows). The 32-B slots of each row are XOR-swizzled by the row so the 8 rows a
 //   32-lane half reads land on 8 different bank slots (conflict-free for both row lengths); as
 //   always with LDS-DMA, the swizzle is applied to the per-lane global source address;
-// * a K-tile runs as 4 phases split along K -- (k 0-31, rows 0-63), (k 0-31, rows 64-127),
-//   (k 32-63, rows 0-63), (k 32-63, rows 64-127) -- because a DMA granule holds whole t-rows: the
-//   t-rows 0-31 of a stage are free after phase 2 and restaged with the K-tile after next there, the
-//   t-rows 32-63 at the next K-tile's phase 1; each half is waited for (counted vmcnt) only one phase
-//   before its first read -- the first half at phase 3 of the previous K-tile, the second half at
-//   phase 1 of its own -- so both have five phases in flight (the round-5 form retired the whole
-//   next K-tile at phase 3: its second half had three);
+// * a K-tile runs as 2 phases split along K -- k 0-31 and k 32-63, each over all 128 rows of the
+//   wave (8 A fragments in two sets of four, FN B fragments: 52 operand VGPRs at FN 5) with a
+//   cluster of 8 x FN MFMAs -- because a DMA granule holds whole t-rows. The wave group that does
+//   not compute reads its fragments, issues DMA and waits, and in this kernel that reader is the
+//   critical path (in-kernel stamps, profiles/gemm8w_phase_balance.md: its segment is longer than
+//   the partner's cluster in every phase, so the K-tile costs the sum of the reader segments, not
+//   the largest): each segment pays the LDS latency and the lgkmcnt(0) drain once whatever it
+//   reads, so two segments of 26 reads cost less than four of 18 / 8 / 18 / 8; and the reader's
+//   VALU is kept to nothing -- every lane carries the LDS address of each fragment's first read in
+//   a register (8 + FN), the second read and the second K-half are immediate offsets, and the
+//   addresses change stage once per K-tile behind the last MFMAs;
+// * DMA order and counted waits. Per K-tile t (stage t & 1), in issue order: P0(t) restages the
+//   other stage's t-rows 32-63 (last read in P1(t-1)) with the second half of K-tile t+1; P1(t)
+//   restages this stage's t-rows 0-31 (last read in P0(t)) with the first half of K-tile t+2. A
+//   half is waited for one phase before its first read (the wave's vmcnt, then the barrier before
+//   the cluster, which the second wave group -- one barrier behind -- passes before the first
+//   group reads). vmcnt retires in issue order, so with n0 / n1 granules per wave in a first /
+//   second half (N01 = n0 + n1 is the same for every wave):
+//     P0(t) retires second half(t):  younger are first half(t+1) [P1(t-1) or the prologue] and
+//           second half(t+1) [just issued] -> vmcnt(N01); on the last K-tile nothing -> vmcnt(0);
+//     P1(t) retires first half(t+1): younger are second half(t+1) [P0(t)] and first half(t+2)
+//           [just issued] -> vmcnt(N01); with no K-tile t+2 only the former -> vmcnt(n1); on the
+//           last K-tile no wait;
+//     prologue: issues K-tile 0 whole and first half(1), retires first half(0) -> vmcnt(N01), or
+//           vmcnt(n1) with a single K-tile.
+//   Each half has two phases (about 1400 cycles) in flight;
 // * fp32 accumulators leave straight from registers, 16 B per lane (4 consecutive output columns, or
 //   4 consecutive output rows when the result is stored transposed), into the DDP bucket or a
 //   split-K slab; rows beyond M (the last, padded row tile) are computed and dropped.
@@ -172,14 +191,24 @@ __global__ __launch_bounds__(NT, 2) void gemm8w_kernel(const WArgs p) {
   const int g4 = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
   // Each fragment = two ds_read_b64_tr_b16 (builtin) joined into one 128-bit MFMA operand; the
   // phase's explicit lgkmcnt(0) before its barrier retires them (WAR against the DMA restaging)
-  auto tr = [&](uint32_t img, int S, int c0, int t) -> s16x4 {
-    const int s = c0 >> 4, f = S == SA ? swz<SA>(t) : swz<SB>(t);
-    const uint32_t off = img + (uint32_t)(t * S + ((s ^ f) << 5) + 8 * pp);
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + off));
-  };
-  auto frag = [&](uint32_t img, int S, int c0, int ks) -> bf16x8 {
-    const int t0 = 32 * ks + 8 * g4 + q;
-    const s16x4 lo = tr(img, S, c0, t0), hi = tr(img, S, c0, t0 + 4);
+  // Each lane keeps the LDS byte address of the first read of every fragment (this K-tile's stage,
+  // k 0-31); the second read (+4 t-rows) and the second K-half (+32 t-rows) are immediate offsets
+  // (neither changes the swizzle of a row: it uses bits 0, 1 and 3 of t only), and the addresses
+  // move to the other stage once per K-tile: 8 + FN adds per K-tile where recomputing them cost
+  // one to two VALU per read in the reader's segment, which is the critical path
+  uint32_t ada[8], adb[FN];
+  {
+    const int t0 = 8 * g4 + q;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      ada[i] = (uint32_t)(t0 * SA + ((((wr * 128 + 16 * i) >> 4) ^ swz<SA>(t0)) << 5) + 8 * pp);
+#pragma unroll
+    for (int j = 0; j < FN; ++j)
+      adb[j] = (uint32_t)(G::A_BYTES + t0 * SB + ((((wc * WTN + 16 * j) >> 4) ^ swz<SB>(t0)) << 5) + 8 * pp);
+  }
+  auto frag = [&](uint32_t addr, int S, int ks) -> bf16x8 {
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + addr + 32 * ks * S));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + addr + 32 * ks * S + 4 * S));
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
   };
 
@@ -188,27 +217,92 @@ __global__ __launch_bounds__(NT, 2) void gemm8w_kernel(const WArgs p) {
   for (int i = 0; i < 8; ++i)
 #pragma unroll
     for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  bf16x8 fa[4], fb[FN];
+  bf16x8 fx[4], fy[4], fb[FN];  // A rows 0-63 / rows 64-127 of the wave's 128, B
   const int arow = wr * 128, bcol = wc * WTN;
-  auto wait_a = [&]() { lgkm0(); };
-  auto wait_ab = [&]() { lgkm0(); };
 
-  auto mma = [&](int i0) {
+  // one phase's MFMA cluster: all 8 row blocks x FN column blocks of one 32-wide K-half
+  auto mma = [&]() {
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 8; ++i)
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
+        const bf16x8& a = i < 4 ? fx[i & 3] : fy[i & 3];
         if constexpr (TRANS)  // lane: C[m = 4(l>>4)+r][n = l&15] -> 4 consecutive m (stored along a row of Cᵀ)
-          acc[i0 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i0 + i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, fb[j], acc[i][j], 0, 0, 0);
         else  // lane: C[m = l&15][n = 4(l>>4)+r] -> 4 consecutive n
-          acc[i0 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i0 + i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], a, acc[i][j], 0, 0, 0);
       }
     __builtin_amdgcn_s_setprio(0);
   };
+  auto read_x = [&](int ks) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) fx[i] = frag(ada[i], SA, ks);
+  };
+  auto read_y = [&](int ks) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) fy[i] = frag(ada[4 + i], SA, ks);
+  };
+  auto read_b = [&](int ks) {
+#pragma unroll
+    for (int j = 0; j < FN; ++j) fb[j] = frag(adb[j], SB, ks);
+  };
+  // the fragment addresses move to the other stage behind the K-tile's last MFMAs (the wave only
+  // waits for the barrier there); opaque to the compiler so that the adds stay there
+  auto next_stage = [&](int t) {
+    const uint32_t d = (t & 1) ? (uint32_t)(-STAGE) : (uint32_t)STAGE;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      ada[i] += d;
+      asm volatile("" : "+v"(ada[i]));
+    }
+#pragma unroll
+    for (int j = 0; j < FN; ++j) {
+      adb[j] += d;
+      asm volatile("" : "+v"(adb[j]));
+    }
+  };
 
-  // ---- prologue: K-tile 0 whole, K-tile 1's first half; only K-tile 0's first half is waited
-  // for here (its second half at phase 1) ---------------------------------------------------------
+#ifdef CS336_G8_STAMP
+  // diagnostic build: kStampTiles k-tiles in the middle of this workgroup's range are stamped at
+  // every phase's entry (3p), after its reads / DMA issue / waits (3p + 1) and after the barrier
+  // before its MFMA cluster (3p + 2); 3 kPhases = after the last barrier. Sums of the three segments
+  // per phase leave through the stamp buffer only (scripts/gemm8w_stamps.py; its rows have room for
+  // four phases)
+  constexpr int kStampTiles = 4, kPhases = 2;
+  const int s_lo = nkt > kStampTiles ? (nkt - kStampTiles) / 2 : 0;
+  uint32_t s_work[4] = {0, 0, 0, 0}, s_wait[4] = {0, 0, 0, 0}, s_mma[4] = {0, 0, 0, 0}, s_cnt = 0;
+  auto stamp = [&]() -> uint32_t {
+    uint64_t v;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v)::"memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return (uint32_t)v;
+  };
+#define CS336_G8W_STAMP(I) \
+  do {                     \
+    if (samp) ts_[I] = stamp(); \
+  } while (0)
+#else
+#define CS336_G8W_STAMP(I) \
+  do {                     \
+  } while (0)
+#endif
+
+  // the two counted waits of a K-tile (constants: header comment)
+  auto wait_h1 = [&](bool more1) {  // retires this K-tile's second half
+    if (more1) vmcnt<N01>();
+    else vmcnt<0>();
+  };
+  auto wait_h0 = [&](bool more1, bool more2) {  // retires the next K-tile's first half
+    if (!more1) return;
+    if (more2) vmcnt<N01>();
+    else if (big0) vmcnt<G::GA + G::GB_LO>();  // younger: K-tile t+1's second half (n1)
+    else vmcnt<G::GA + G::GB_HI>();
+  };
+
+  // ---- prologue: K-tile 0 whole, K-tile 1's first half; only K-tile 0's first half is waited for
+  // here (its second half at phase 0) ------------------------------------------------------------
   if (nkt > 0) {
     CS336_G8W_ISSUE(0, 0, 0);
     CS336_G8W_ISSUE(1, 0, 0);
@@ -224,57 +318,72 @@ __global__ __launch_bounds__(NT, 2) void gemm8w_kernel(const WArgs p) {
   if (wr == 1) sbarrier();
 
   for (int t = 0; t < nkt; ++t) {
-    const uint32_t st = (uint32_t)((t & 1) * STAGE);
-    // P0: k 0-31, rows 0-63 (+ all column tiles); restage K-tile t+1's second half
-    if (t + 1 < nkt) CS336_G8W_ISSUE(1, t + 1, (t + 1) & 1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fa[i] = frag(st, SA, arow + 16 * i, 0);
-#pragma unroll
-    for (int j = 0; j < FN; ++j) fb[j] = frag(st + G::A_BYTES, SB, bcol + 16 * j, 0);
-    wait_ab();
+    const bool more1 = t + 1 < nkt, more2 = t + 2 < nkt;
+#ifdef CS336_G8_STAMP
+    const bool samp = t >= s_lo && t < s_lo + kStampTiles;
+    uint32_t ts_[3 * kPhases + 1] = {};
+#endif
+    // P0: k 0-31, all 128 rows; restage the other stage's second half with K-tile t+1; retire this
+    // K-tile's second half (read in P1)
+    CS336_G8W_STAMP(0);
+    if (more1) CS336_G8W_ISSUE(1, t + 1, (t + 1) & 1);
+    read_x(0);
+    read_y(0);
+    read_b(0);
+    wait_h1(more1);
+    lgkm0();
+    CS336_G8W_STAMP(1);
     sbarrier();
-    mma(0);
+    CS336_G8W_STAMP(2);
+    mma();
     sbarrier();
-    // P1: k 0-31, rows 64-127; retire this K-tile's second half (read from P2 on): issued at the
-    // previous K-tile's P0, it has had five phases in flight
+    // P1: k 32-63; restage this stage's first half with K-tile t+2; retire K-tile t+1's first half
+    CS336_G8W_STAMP(3);
+    if (more2) CS336_G8W_ISSUE(0, t + 2, t & 1);
+    read_x(1);
+    read_y(1);
+    read_b(1);
+    wait_h0(more1, more2);
+    lgkm0();
+    CS336_G8W_STAMP(4);
+    sbarrier();
+    CS336_G8W_STAMP(5);
+    mma();
+    next_stage(t);
+    sbarrier();
+    CS336_G8W_STAMP(6);
+#ifdef CS336_G8_STAMP
+    if (samp) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) fa[i] = frag(st, SA, arow + 64 + 16 * i, 0);
-    if (t + 1 < nkt) vmcnt<N01>();  // younger: K-tile t+1's two halves
-    else vmcnt<0>();
-    wait_a();
-    sbarrier();
-    mma(4);
-    sbarrier();
-    // P2: k 32-63, rows 0-63; restage this stage's first half with K-tile t+2
-    if (t + 2 < nkt) CS336_G8W_ISSUE(0, t + 2, t & 1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fa[i] = frag(st, SA, arow + 16 * i, 1);
-#pragma unroll
-    for (int j = 0; j < FN; ++j) fb[j] = frag(st + G::A_BYTES, SB, bcol + 16 * j, 1);
-    wait_ab();
-    sbarrier();
-    mma(0);
-    sbarrier();
-    // P3: k 32-63, rows 64-127; retire K-tile t+1's first half (read at its P0); its second half and
-    // K-tile t+2's first half stay in flight
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fa[i] = frag(st, SA, arow + 64 + 16 * i, 1);
-    if (t + 1 < nkt) {
-      if (t + 2 < nkt) {
-        vmcnt<N01>();  // younger: K-tile t+1's second half (P0), K-tile t+2's first half (P2)
-      } else if (big0) {
-        vmcnt<G::GA + G::GB_LO>();  // younger: K-tile t+1's second half (n1)
-      } else {
-        vmcnt<G::GA + G::GB_HI>();
+      for (int ph = 0; ph < kPhases; ++ph) {
+        s_work[ph] += ts_[3 * ph + 1] - ts_[3 * ph];
+        s_wait[ph] += ts_[3 * ph + 2] - ts_[3 * ph + 1];
+        s_mma[ph] += ts_[3 * ph + 3] - ts_[3 * ph + 2];
       }
+      ++s_cnt;
     }
-    wait_a();
-    sbarrier();
-    mma(4);
-    sbarrier();
+#endif
   }
 #undef CS336_G8W_ISSUE
+#undef CS336_G8W_STAMP
   if (wr == 0) sbarrier();
+#ifdef CS336_G8_STAMP
+  // 4 rows of 8 per workgroup: wave group g -> rows 2g (work[4], wait[4]) and 2g + 1 (mma[4],
+  // stamped k-tiles, k-tiles, HW_ID, XCC_ID)
+  if (p.stamps && lane == 0 && wc == 0) {
+    uint32_t hw, xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    uint64_t* o = p.stamps + 32 * ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) + 16 * wr;
+#pragma unroll
+    for (int ph = 0; ph < kPhases; ++ph) {
+      o[ph] = s_work[ph];
+      o[4 + ph] = s_wait[ph];
+      o[8 + ph] = s_mma[ph];
+    }
+    o[12] = s_cnt; o[13] = (uint64_t)nkt; o[14] = hw; o[15] = xcc;
+  }
+#endif
 
   // ---- epilogue: fp32 straight from the accumulators, 16 B per lane ----------------------------
   float* c = p.c + (int64_t)split * p.slab_stride;
@@ -312,8 +421,10 @@ __global__ __launch_bounds__(NT, 2) void gemm8w_kernel(const WArgs p) {
 }
 
 template <int FN, int TRANS>
-void launch_wt(const WArgs& p, hipStream_t s) {
+void launch_wt(const WArgs& p_in, hipStream_t s) {
+  WArgs p = p_in;
   const dim3 grid((unsigned)(((p.M + BM - 1) / BM) * (p.N / (64 * FN))), (unsigned)p.splits), block(NT);
+  if (4 * (int64_t)grid.x * grid.y > p.stamp_rows) p.stamps = nullptr;
   hipLaunchKernelGGL((gemm8w_kernel<FN, TRANS>), grid, block, 0, s, p);
 }
 

@@ -42,6 +42,13 @@ for r in json.load(open('gpurun_out/flash4096.json')):
     stamps)  # in-kernel gemm8 phase stamps (CS336_G8_STAMP variant build)
       CS336_LIB=cs336_systems/_native/variants/stamp/libcs336_hip.so timeout -k 10 300 python -u scripts/gemm8_stamps.py ${STAMP_ARGS:-} --json gpurun_out/gemm8_stamps.json > gpurun_out/gemm8_stamps.log 2>&1 || { tail -30 gpurun_out/gemm8_stamps.log; exit 1; }
       cat gpurun_out/gemm8_stamps.log ;;
+    wstamps)  # in-kernel gemm8w phase stamps, per wave group (the same CS336_G8_STAMP variant build); rows on stdout
+      CS336_LIB=cs336_systems/_native/variants/stamp/libcs336_hip.so timeout -k 10 300 python -u scripts/gemm8w_stamps.py ${STAMP_ARGS:-} 2>&1 || exit 1 ;;
+    dwbits)  # the four XL weight gradients, base variant lib vs this tree's lib, bit for bit (check exits 1 on a difference)
+      dump=$(mktemp --suffix .pt)
+      CS336_LIB=cs336_systems/_native/variants/base/libcs336_hip.so timeout -k 10 240 python -u scripts/gemm8w_bitwise.py dump "$dump" 2>&1 && \
+      timeout -k 10 240 python -u scripts/gemm8w_bitwise.py check "$dump" 2>&1 || { rm -f "$dump"; exit 1; }
+      rm -f "$dump" ;;
     graphab)  # eager step vs the whole step captured in one HIP graph, same box
       timeout -k 10 900 python scripts/ab.py bench "eager:" "graphs:PYTHONFAULTHANDLER=1:--graphs on" --rounds ${AB_ROUNDS:-2} --steps 10 --timeout 300 > gpurun_out/graphab.log 2>&1 || { tail -30 gpurun_out/graphab.log; exit 1; }
       tail -8 gpurun_out/graphab.log ;;
