@@ -20,6 +20,15 @@ arms (the uncached one takes minutes at context 4096).
     python -m cs336_systems.bench.decode --json profiles/decode_attention.json
     python -m cs336_systems.bench.decode --no-e2e --batch 8 --kv-len 4096
     python -m cs336_systems.bench.decode --no-kernel --skinny --arms cached graph --json profiles/decode_graph.json
+
+Chunk tables (``--chunk``): ``ops.decode_attention_chunk`` (``csrc/flash_attn/fa_decode_chunk.hip``) at
+n in {1, 2, 4, 8, 16} query rows over the same (B, H, d, kv_len) points: us, GB/s of K+V bytes (read
+once) and the time of the n sequential ``ops.decode_attention`` launches it replaces. With
+``--arms verify``: the graph-replayed step of ``xl`` in bf16 at B = 1 for ``DecodeGraph(tokens=t)``,
+t in {1, 2, 4, 8, 16}, timed interleaved on one cache (truncated back after every step) -- the cost of
+a speculative verify step relative to an ordinary one.
+
+    python -m cs336_systems.bench.decode --chunk --arms verify --json profiles/decode_chunk.json
 """
 
 from __future__ import annotations
@@ -70,6 +79,80 @@ def kernel_row(B: int, H: int, d: int, kv_len: int, warmup: int = 10, rep: int =
     del q, k, v
     torch.cuda.empty_cache()
     return row
+
+
+CHUNK_N = (1, 2, 4, 8, 16)
+
+
+def chunk_row(B: int, H: int, d: int, kv_len: int, n: int, warmup: int = 10, rep: int = 50) -> dict:
+    dev, dt = "cuda", torch.bfloat16
+    torch.manual_seed(0)
+    q = torch.randn(B, n, H, d, device=dev, dtype=dt)
+    k = torch.randn(B, H, kv_len, d, device=dev, dtype=dt)
+    v = torch.randn(B, H, kv_len, d, device=dev, dtype=dt)
+    lens = torch.full((B,), kv_len, dtype=torch.int32, device=dev)
+    kv_bytes = 2.0 * B * H * kv_len * d * k.element_size()
+    qt = int(torch.ops.cs336.fa_decode_chunk_qt(n))
+    row = dict(B=B, H=H, d=d, kv_len=kv_len, n=n, dtype="bf16", kv_mbytes=kv_bytes / 2**20, query_tile=qt,
+               splits=int(torch.ops.cs336.fa_decode_splits(B * ((n + qt - 1) // qt), H, d, k.element_size(), kv_len)))
+    q1 = [q[:, i].contiguous() for i in range(n)]
+
+    def sequential():
+        for qi in q1:
+            ops.decode_attention(qi, k, v, lens)
+
+    for key, fn in (("chunk", lambda: ops.decode_attention_chunk(q, k, v, lens)), ("sequential", sequential)):
+        med, lo, hi = do_bench(fn, warmup=warmup, rep=rep)
+        row[f"{key}_us"], row[f"{key}_us_q20"], row[f"{key}_us_q80"] = med * 1e3, lo * 1e3, hi * 1e3
+    row["chunk_gbs"] = kv_bytes / (row["chunk_us"] * 1e-6) / 1e9
+    row["chunk_hbm_frac"] = row["chunk_gbs"] / HBM_ACHIEVABLE_GBS
+    row["speedup_vs_sequential"] = row["sequential_us"] / row["chunk_us"]
+    o, _ = ops.decode_attention_chunk(q, k, v, lens)
+    o1, _ = ops.decode_attention(q1[-1], k, v, lens)  # the last query sees every key
+    row["max_abs_diff_last_query_vs_decode"] = (o[:, -1].float() - o1.float()).abs().max().item()
+    del q, k, v
+    torch.cuda.empty_cache()
+    return row
+
+
+def verify_rows(model_size: str, ctx: int = 512, B: int = 1, prefix: int = 256, rep: int = 50) -> list[dict]:
+    """Replayed step time of ``DecodeGraph(tokens=t)`` for every t of CHUNK_N on ONE cache of ``prefix``
+    tokens, interleaved (t varies fastest; the cache is truncated back after every step), HIP events
+    around the replay."""
+    from ..models import DecodeGraph, build_model
+    from ..models.kv_cache import KVCache
+
+    torch.manual_seed(0)
+    model = build_model(model_size, ctx, device="cuda").to(torch.bfloat16).eval()
+    x = torch.randint(0, model.vocab_size, (B, prefix + max(CHUNK_N)), device="cuda")
+    cache = KVCache(model, B)
+    model.forward_cached(x[:, :prefix], cache)
+    graphs = {t: DecodeGraph(model, cache, capture=True, tokens=t) for t in CHUNK_N}
+    times = {t: [] for t in CHUNK_N}
+    for r in range(rep + 5):
+        for t, dg in graphs.items():
+            tok = x[:, prefix:prefix + t]
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            dg.step(tok)
+            b.record()
+            b.synchronize()
+            cache.truncate(prefix)
+            if r >= 5:  # the first rounds warm clocks and caches
+                times[t].append(a.elapsed_time(b))
+    rows = []
+    for t in CHUNK_N:
+        ts = sorted(times[t])
+        rows.append(dict(model=model_size, context_length=ctx, B=B, cached=prefix, tokens=t, dtype="bf16",
+                         step_ms=ts[len(ts) // 2], step_ms_q20=ts[len(ts) // 5], step_ms_q80=ts[len(ts) * 4 // 5]))
+    for r in rows:
+        r["vs_one_token"] = r["step_ms"] / rows[0]["step_ms"]
+        # a round of k = tokens - 1 proposals costs one verify step (plus the draft) and yields
+        # 1 + accepted tokens: below this many accepted tokens per round it loses to plain steps
+        r["break_even_accepted_per_round"] = r["vs_one_token"] - 1.0
+    del graphs, model, cache
+    torch.cuda.empty_cache()
+    return rows
 
 
 SKINNY_M = (1, 8, 16)
@@ -156,7 +239,10 @@ def main(argv=None):
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--model", default="xl")
     ap.add_argument("--skinny", action="store_true", help="the skinny-M GEMM table (xl and 2.7b projections)")
-    ap.add_argument("--arms", nargs="+", default=["cached", "uncached", "graph"], choices=sorted(ARMS))
+    ap.add_argument("--chunk", action="store_true",
+                    help="the multi-token tables: decode_attention_chunk rows instead of the single-token sweep, and "
+                         "(with --arms verify) the replayed n-token step; no generate arms")
+    ap.add_argument("--arms", nargs="+", default=["cached", "uncached", "graph"], choices=sorted(ARMS) + ["verify"])
     ap.add_argument("--json", default=None)
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -164,6 +250,32 @@ def main(argv=None):
     if not ops.load_ext():
         raise SystemExit(ops.load_error())
     out = dict(hbm_achievable_gbs=HBM_ACHIEVABLE_GBS, kernel=[], skinny=[], e2e=[])
+    if a.chunk:
+        from ..utils.gpu_monitor import GpuSampler
+
+        out.update(chunk=[], verify=[])
+        with GpuSampler(torch.device("cuda", torch.cuda.current_device())) as sampler:  # the box's clocks
+            if not a.no_kernel:
+                for shape in a.shapes:
+                    H, d = (int(s) for s in shape.split("x"))
+                    for B in a.batch:
+                        for kv in a.kv_len:
+                            for n in CHUNK_N:
+                                r = chunk_row(B, H, d, kv, n, rep=a.rep)
+                                out["chunk"].append(r)
+                                print(json.dumps(r), flush=True)
+            if "verify" in a.arms:
+                for r in verify_rows(a.model, rep=a.rep):
+                    out["verify"].append(r)
+                    print(json.dumps(r), flush=True)
+        out["gpu_clocks"] = sampler.summary()
+        print(json.dumps(dict(gpu_clocks=out["gpu_clocks"])), flush=True)
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return out
+    if "verify" in a.arms:
+        raise SystemExit("--arms verify needs --chunk")
     if not a.no_kernel:
         for shape in a.shapes:
             H, d = (int(s) for s in shape.split("x"))

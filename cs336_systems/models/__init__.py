@@ -1,6 +1,7 @@
 from .configs import DEFAULT_THETA, DEFAULT_VOCAB, MODEL_CONFIGS, get_model_config, param_count, train_flops_per_token
 from .decode_graph import DecodeGraph
 from .kv_cache import KVCache
+from .speculative import speculative_generate
 from .transformer import (
     BasicsTransformerLM,
     CausalMultiHeadSelfAttention,
@@ -49,4 +50,5 @@ __all__ = [
     "scaled_dot_product_attention",
     "silu",
     "softmax",
+    "speculative_generate",
 ]

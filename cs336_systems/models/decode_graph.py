@@ -19,6 +19,12 @@ in-place weight updates are picked up by the next replay; ``model.to(...)`` or a
 re-allocates the parameters invalidates the graph (not detected). An fp32 model under autocast works
 (construct and step under the same autocast context: the weight casts are captured) but re-casts
 every weight per token -- hold the model in bf16.
+
+``tokens=n`` (n > 1) captures the n-token chunk step instead (``ops.kv_append_rope_chunk`` and
+``ops.decode_attention_chunk``): the verify step of speculative decoding, or a fixed-size follow-up
+chunk. Its projections have ``B * n`` rows; up to 16 they run the skinny kernel, which reads every
+weight once whatever the row count, and above that the ordinary GEMM path. ``cache.truncate`` is, like
+``reset``, an in-place update of ``cache.lengths`` and leaves the graph valid.
 """
 
 from __future__ import annotations
@@ -29,9 +35,10 @@ from ..ops import gemm
 
 
 class DecodeGraph:
-    """``logits = dg.step(tok)``: ``tok`` (B, 1) int64 -> (B, 1, vocab), the cache advanced by one."""
+    """``logits = dg.step(tok)``: ``tok`` (B, tokens) int64 -> (B, tokens, vocab), the cache advanced
+    by ``tokens`` (default 1)."""
 
-    def __init__(self, model, cache, capture: bool = True, warmup: int = 2):
+    def __init__(self, model, cache, capture: bool = True, warmup: int = 2, tokens: int = 1):
         if getattr(model, "tensor_parallel", None) is not None or any(
                 layer.attn.context_parallel is not None for layer in model.layers):
             raise NotImplementedError("DecodeGraph does not support tensor / context parallelism")
@@ -39,14 +46,16 @@ class DecodeGraph:
             raise ValueError("cache was built for a different number of layers")
         if capture and not cache.k.is_cuda:
             raise ValueError("DecodeGraph(capture=True) captures HIP graphs: the model and cache must be on a GPU")
-        self.model, self.cache = model, cache
+        if int(tokens) != tokens or tokens < 1:
+            raise ValueError("DecodeGraph needs tokens >= 1")
+        self.model, self.cache, self.tokens = model, cache, int(tokens)
         self.graph = None
         if not capture:
             return
         dev = cache.k.device
-        self.tok = torch.zeros(cache.batch, 1, dtype=torch.int64, device=dev)
+        self.tok = torch.zeros(cache.batch, self.tokens, dtype=torch.int64, device=dev)
         # Warm-up and capture leave the cache as they found it: a warm-up step writes its K / V rows
-        # at index ``length``, which no one reads (on a full cache the append kernel stores nothing),
+        # from index ``length`` on, which no one reads (past the cache's end the append kernels store nothing),
         # and lengths / length are put back; capturing executes nothing but the host bookkeeping.
         lengths, length = cache.lengths.clone(), cache.length
         self.stream = torch.cuda.Stream(device=dev)
@@ -67,26 +76,28 @@ class DecodeGraph:
 
     @torch.no_grad()
     def _run(self, tok: torch.Tensor) -> torch.Tensor:
-        """The step both modes run: the decode branch of ``forward_cached`` (also on an empty cache,
-        where the warm-up's row lands at index 0, unread) with the fixed attention bound."""
+        """The step both modes run: the decode (or, for ``tokens > 1``, chunk) branch of
+        ``forward_cached`` (also on an empty cache, where the warm-up's rows land at index 0, unread)
+        with the fixed attention bound."""
         with gemm.skinny_decode():
             return self.model._forward_cached(tok, self.cache, max(self.cache.length, 1), self.cache.max_len)
 
     def step(self, tok: torch.Tensor) -> torch.Tensor:
-        """Logits (B, 1, vocab) of the token ``tok`` (B, 1) that follows the cached ones; the cache
-        then holds it too. With ``capture=True`` the result is the graph's static output buffer: it
+        """Logits (B, tokens, vocab) of the tokens ``tok`` (B, tokens) that follow the cached ones; the
+        cache then holds them too. With ``capture=True`` the result is the graph's static output buffer: it
         stays valid until the next ``step``, which overwrites it. A failed check changes nothing."""
         cache = self.cache
-        if tok.dim() != 2 or tok.shape[0] != cache.batch or tok.shape[1] != 1:
-            raise ValueError(f"DecodeGraph.step takes (B, 1) token ids with B = {cache.batch}")
+        n = self.tokens
+        if tok.dim() != 2 or tok.shape[0] != cache.batch or tok.shape[1] != n:
+            raise ValueError(f"DecodeGraph.step takes (B, {n}) token ids with B = {cache.batch}")
         if cache.length < 1:
             raise ValueError("DecodeGraph.step on an empty cache: prefill first (forward_cached on the prompt)")
-        if cache.length >= min(cache.max_len, self.model.context_length):
-            raise ValueError(f"{cache.length} cached + 1 new token exceed the cache (max_len {cache.max_len}, "
-                             f"context_length {self.model.context_length})")
+        if cache.length + n > min(cache.max_len, self.model.context_length):
+            raise ValueError(f"{cache.length} cached + {n} new token{'s' if n > 1 else ''} exceed the cache "
+                             f"(max_len {cache.max_len}, context_length {self.model.context_length})")
         if self.graph is None:
             return self._run(tok)
         self.tok.copy_(tok)
         self.graph.replay()
-        cache.length += 1  # the captured ``lengths += 1`` advanced the device tensor
+        cache.length += n  # the captured ``lengths += n`` advanced the device tensor
         return self.logits

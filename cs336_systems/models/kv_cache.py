@@ -52,6 +52,16 @@ class KVCache:
         self.lengths.zero_()
         self.length = 0
 
+    def truncate(self, length: int) -> None:
+        """Forget the tokens at and beyond ``length`` (rejected draft tokens of a speculative round;
+        their rows stay and are overwritten). In place and without a host sync, so a ``DecodeGraph``
+        tied to this cache stays valid."""
+        length = int(length)
+        if length < 0 or length > self.length:
+            raise ValueError(f"truncate({length}) on a cache of length {self.length}")
+        self.lengths.fill_(length)
+        self.length = length
+
     def advance(self, n: int) -> None:
         self.lengths += n
         self.length += n

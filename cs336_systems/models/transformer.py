@@ -376,9 +376,10 @@ class CausalMultiHeadSelfAttention(nn.Module):
         ``v_cache`` this layer's (B, H, max_len, dk) cache views. ``start == 0``: prefill -- the
         ordinary causal attention over the n tokens at positions 0..n-1, whose rotated K and V are
         copied into cache rows [0, n). Otherwise one decode step (n == 1): ``pos`` (B,) int32 is the
-        new token's slot and RoPE position, ``kv_len = pos + 1`` its key count. ``max_kv_len``: the
-        host-side bound of ``kv_len`` that picks the decode kernel's split count (default
-        ``start + 1``; a captured step passes a fixed one)."""
+        new token's slot and RoPE position, ``kv_len = pos + 1`` its key count; or a chunk step
+        (n > 1) over the chunk ops: ``pos`` is the slot of the chunk's first token, ``kv_len = pos + n``
+        the key count of its last. ``max_kv_len``: the host-side bound of ``kv_len`` that picks the
+        decode kernel's split count (default ``start + n``; a captured step passes a fixed one)."""
         B, n, _ = x3.shape
         H, dk = self.num_heads, self.d_k
         w = [self.q_proj.weight, self.k_proj.weight, self.v_proj.weight]
@@ -389,7 +390,15 @@ class CausalMultiHeadSelfAttention(nn.Module):
                 qkv = torch.cat([self.q_proj(x3), self.k_proj(x3), self.v_proj(x3)], dim=-1)
         if qkv.dtype != k_cache.dtype:
             raise ValueError(f"KV cache dtype {k_cache.dtype} does not match the compute dtype {qkv.dtype}")
-        if start > 0:
+        if start > 0 and n > 1:
+            with annotate("kv_append_rope_chunk"):
+                q = ops.kv_append_rope_chunk(qkv, self.positional_encoder.cos, self.positional_encoder.sin, pos,
+                                             k_cache, v_cache)
+            with annotate("decode_attention_chunk"):
+                o, _ = ops.decode_attention_chunk(q, k_cache, v_cache, kv_len,
+                                                  max_kv_len=start + n if max_kv_len is None else max_kv_len)
+            o = o.reshape(B, n, H * dk)
+        elif start > 0:
             with annotate("kv_append_rope"):
                 q = ops.kv_append_rope(qkv.view(B, 3 * H * dk), self.positional_encoder.cos, self.positional_encoder.sin,
                                        pos, k_cache, v_cache)
@@ -600,14 +609,20 @@ class BasicsTransformerLM(nn.Module):
             return self.lm_head(y)
 
     @torch.no_grad()
-    def forward_cached(self, x: torch.Tensor, cache) -> torch.Tensor:
+    def forward_cached(self, x: torch.Tensor, cache, chunk: bool = False) -> torch.Tensor:
         """Logits ``(B, n, vocab)`` of the ``n`` tokens ``x`` that follow the ``cache.length`` tokens
         already in ``cache`` (a :class:`~cs336_systems.models.kv_cache.KVCache`); the cache then
         holds them too. On an empty cache this is the prefill (any ``n >= 1``: the ordinary forward,
         with every layer's rotated K and V copied into the cache); afterwards one token per call
         (``n == 1``): per layer the QKV projection of that token alone, ``ops.kv_append_rope`` and
         ``ops.decode_attention`` over the cached keys -- O(1) projection and O(length) attention work
-        per token instead of a forward over the whole window."""
+        per token instead of a forward over the whole window.
+
+        ``chunk=True`` also takes ``n > 1`` tokens on a non-empty cache (a follow-up prompt, a prefill
+        in chunks, the verify step of speculative decoding): per layer the QKV projection of the n
+        tokens, ``ops.kv_append_rope_chunk`` and ``ops.decode_attention_chunk``, in which token ``i``
+        attends to the cached keys and the chunk's tokens up to itself. ``n == 1`` and the prefill
+        take the same paths whatever ``chunk`` is."""
         if getattr(self, "tensor_parallel", None) is not None or any(
                 layer.attn.context_parallel is not None for layer in self.layers):
             raise NotImplementedError("forward_cached does not support tensor / context parallelism")
@@ -621,7 +636,7 @@ class BasicsTransformerLM(nn.Module):
         start = cache.length
         if n < 1:
             raise ValueError("forward_cached needs at least one token")
-        if start > 0 and n > 1:
+        if start > 0 and n > 1 and not chunk:
             raise NotImplementedError("chunked prefill (n > 1 on a non-empty cache) is not supported")
         if start + n > min(cache.max_len, self.context_length):
             raise ValueError(f"{start} cached + {n} new tokens exceed the cache (max_len {cache.max_len}, "
@@ -630,7 +645,7 @@ class BasicsTransformerLM(nn.Module):
 
     def _forward_cached(self, x: torch.Tensor, cache, start: int, max_kv_len: int | None = None) -> torch.Tensor:
         """The body of :meth:`forward_cached` after its checks: the prefill (``start == 0``) or one
-        decode step (``start > 0``) over the layers, the cache advanced by the tokens of ``x``.
+        decode / chunk step (``start > 0``) over the layers, the cache advanced by the tokens of ``x``.
         ``max_kv_len``: see ``CausalMultiHeadSelfAttention.forward_cached``. Nothing here reads the
         host mirror ``cache.length`` or synchronizes the host, so a decode step can be captured into
         a HIP graph (``models/decode_graph.py``)."""
@@ -638,7 +653,7 @@ class BasicsTransformerLM(nn.Module):
         pos = kv_len = None
         if start > 0:  # once per step, shared by all layers
             pos = cache.lengths
-            kv_len = cache.lengths + 1
+            kv_len = cache.lengths + n
         with annotate("embed"):
             h = self.token_embeddings(x)
         n_layers = len(self.layers)
@@ -674,6 +689,8 @@ class BasicsTransformerLM(nn.Module):
         eos_token_id: int | None = None,
         use_cache: bool = False,
         graph=False,
+        draft=None,
+        draft_tokens: int = 4,
     ) -> torch.Tensor:
         """Autoregressive sampling (``model.py:255-310``) with a working top-k filter (the
         reference's ``masked_fill`` is not in place and its threshold broadcast is wrong for B>1).
@@ -687,8 +704,24 @@ class BasicsTransformerLM(nn.Module):
         captured into a HIP graph over the skinny-M GEMM kernel (:class:`DecodeGraph`) and every
         cached step is one replay. ``graph=<DecodeGraph>`` reuses a caller-owned graph of this model
         and batch size (its cache is reset and prefilled), which saves the capture per call.
-        Sampling stays eager."""
+        Sampling stays eager.
+
+        ``draft=<model>``: greedy speculative decoding (``models/speculative.py``): the draft proposes
+        ``draft_tokens`` tokens per round and this model verifies them in one chunk step; the output
+        is exactly the greedy one. Needs ``use_cache=True``, ``top_k == 1`` and a bool ``graph``;
+        sampling from a draft is not supported."""
         from .decode_graph import DecodeGraph
+
+        if draft is not None:
+            from .speculative import speculative_generate
+
+            if not use_cache:
+                raise ValueError("generate(draft=...) needs use_cache=True")
+            if top_k != 1:
+                raise ValueError("generate(draft=...) is greedy: it needs top_k == 1")
+            if not isinstance(graph, bool):
+                raise ValueError("generate(draft=...) takes graph=True or False")
+            return speculative_generate(self, draft, x, max_new_tokens, draft_tokens, eos_token_id, graph)[0]
 
         if x.dim() == 1:
             x = x.unsqueeze(0)

@@ -4,7 +4,8 @@ oracle in tests) and a hand-written HIP/CDNA4 kernel (used for GPU tensors)."""
 from ._ext import backend, ext_available, get_backend, load_error, load_ext, set_backend, use_hip
 from .adamw import FusedAdamW, clip_grad_norm_, multi_tensor_l2norm
 from .cross_entropy import cross_entropy, cross_entropy_ref
-from .decode import decode_attention, decode_attention_ref, kv_append_rope, kv_append_rope_ref
+from .decode import (decode_attention, decode_attention_chunk, decode_attention_chunk_ref, decode_attention_ref,
+                     kv_append_rope, kv_append_rope_chunk, kv_append_rope_chunk_ref, kv_append_rope_ref)
 from .flash_attention import (
     FlashAttentionHIP,
     FlashAttentionTorch,
@@ -31,8 +32,12 @@ __all__ = [
     "cross_entropy",
     "cross_entropy_ref",
     "decode_attention",
+    "decode_attention_chunk",
+    "decode_attention_chunk_ref",
     "decode_attention_ref",
     "kv_append_rope",
+    "kv_append_rope_chunk",
+    "kv_append_rope_chunk_ref",
     "kv_append_rope_ref",
     "FlashAttentionHIP",
     "FlashAttentionTorch",

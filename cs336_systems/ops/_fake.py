@@ -172,6 +172,19 @@ if hasattr(torch.ops.cs336, "fa_decode"):  # (absent from libraries built before
         return qkv.new_empty((B, H, D))
 
 
+if hasattr(torch.ops.cs336, "fa_decode_chunk"):  # (absent from libraries built before the chunk step: A/B baselines)
+
+    @register_fake("cs336::fa_decode_chunk")
+    def _fa_decode_chunk(q, k_cache, v_cache, kv_len, scale, max_kv_len, splits=0):
+        B, n, H, D = q.shape
+        return q.new_empty((B, n, H, D)), q.new_empty((B, n, H), dtype=torch.float32)
+
+    @register_fake("cs336::kv_append_rope_chunk")
+    def _kv_append_rope_chunk(qkv, cos, sin, pos, k_cache, v_cache):
+        B, H, _, D = k_cache.shape
+        return qkv.new_empty((B, qkv.shape[1], H, D))
+
+
 if hasattr(torch.ops.cs336, "gemm_skinny"):  # (absent from libraries built before the decode graph: A/B baselines)
 
     @register_fake("cs336::gemm_skinny")

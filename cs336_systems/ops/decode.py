@@ -12,6 +12,14 @@ used and may hold anything.
 (B, H, d); rotated k and plain v are written into row ``pos[b]`` of every (b, h) cache plane. A
 ``pos[b]`` outside the cache stores nothing.
 
+``decode_attention_chunk`` / ``kv_append_rope_chunk`` (``csrc/flash_attn/fa_decode_chunk.hip``): the
+same for ``n >= 1`` tokens per sequence -- a follow-up prompt, a prefill in chunks or the verify step
+of speculative decoding. ``q`` is (B, n, H, d) and ``kv_len[b]`` counts the keys AFTER the chunk's own
+rows were appended: query ``i`` sees keys ``[0, kv_len[b] - (n - 1 - i))``, clamped to
+``[0, max_len]`` (bottom-right-aligned causality); a query whose bound is <= 0 gives ``o = 0``,
+``lse = -inf``. ``qkv`` is (B, n, 3*H*d), ``pos[b]`` the slot of the chunk's first token; token ``i``
+is rotated at and written to ``pos[b] + i``, and a token without a slot stores nothing.
+
 The HIP kernels take head dims 32 / 64 / 80 / 128 (the ones the model's fused attention path takes);
 other head dims run the reference. On a GPU with the HIP backend a missing extension raises.
 """
@@ -94,3 +102,77 @@ def kv_append_rope(qkv, cos, sin, pos, k_cache, v_cache):
         return ops().kv_append_rope(qkv, cos.float().contiguous(), sin.float().contiguous(), pos.contiguous(),
                                     k_cache, v_cache)
     return kv_append_rope_ref(qkv, cos, sin, pos, k_cache, v_cache)
+
+
+def decode_attention_chunk_ref(q, k_cache, v_cache, kv_len, scale=None):
+    """``q`` (B, n, H, d): masked softmax of query ``i`` over its first ``kv_len[b] - (n - 1 - i)``
+    keys, fp32 (or fp64) math. Cache rows no query reads are replaced before any arithmetic, so NaNs
+    there cannot leak. Returns ``o`` (B, n, H, d) and ``lse`` (B, n, H) fp32."""
+    B, n, H, d = q.shape
+    scale = 1.0 / math.sqrt(d) if scale is None else scale
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    N = k_cache.shape[2]
+    back = torch.arange(n - 1, -1, -1, device=q.device)  # n - 1 - i
+    bound = (kv_len.to(torch.int64)[:, None] - back[None, :]).clamp(0, N)  # (B, n)
+    valid = torch.arange(N, device=q.device)[None, None, :] < bound[:, :, None]  # (B, n, N)
+    vm = valid[:, -1][:, None, :, None]  # the last query's range holds every other one
+    k = torch.where(vm, k_cache.to(ct), 0.0)
+    v = torch.where(vm, v_cache.to(ct), 0.0)
+    s = torch.einsum("bnhd,bhkd->bnhk", q.to(ct), k) * scale
+    s = torch.where(valid[:, :, None, :], s, float("-inf"))
+    lse = torch.logsumexp(s, dim=-1)
+    p = torch.exp(s - torch.where(torch.isinf(lse), 0.0, lse)[..., None])  # empty row: exp(-inf) = 0
+    o = torch.einsum("bnhk,bhkd->bnhd", p, v)
+    return o.to(q.dtype), lse.float()
+
+
+def kv_append_rope_chunk_ref(qkv, cos, sin, pos, k_cache, v_cache):
+    """No per-token loop and no host sync: every cache row picks its token (or keeps its value)."""
+    B, H, max_len, d = k_cache.shape
+    n = qkv.shape[1]
+    q, k, v = (t.transpose(1, 2) for t in qkv.reshape(B, n, 3, H, d).unbind(2))  # (B, H, n, d)
+    lim = min(max_len, cos.shape[0])
+    slot = pos.to(torch.int64)[:, None] + torch.arange(n, device=qkv.device)[None, :]  # (B, n)
+    ok = (slot >= 0) & (slot < lim)
+    p = slot.clamp(0, lim - 1)
+    q_rot = rope_ref(q, cos, sin, p[:, None, :])
+    k_rot = rope_ref(k, cos, sin, p[:, None, :])
+    # cache row r of sequence b takes token r - pos[b] if that is one of the chunk's and r has a slot
+    r = torch.arange(max_len, device=qkv.device)[None, :]
+    t = r - pos.to(torch.int64)[:, None]  # (B, max_len)
+    take = ((t >= 0) & (t < n) & (r < lim))[:, None, :, None]
+    idx = t.clamp(0, n - 1)[:, None, :, None].expand(B, H, max_len, d)
+    k_cache.copy_(torch.where(take, k_rot.gather(2, idx).to(k_cache.dtype), k_cache))
+    v_cache.copy_(torch.where(take, v.gather(2, idx).to(v_cache.dtype), v_cache))
+    q_rot = torch.where(ok[:, None, :, None], q_rot, torch.zeros_like(q_rot))
+    return q_rot.transpose(1, 2).contiguous()  # (B, n, H, d)
+
+
+def decode_attention_chunk(q, k_cache, v_cache, kv_len, scale=None, max_kv_len=None, splits=0):
+    """``q`` (B, n, H, d) -> ``o`` (B, n, H, d), ``lse`` (B, n, H). ``max_kv_len`` and ``splits`` as in
+    :func:`decode_attention`."""
+    d = q.shape[-1]
+    scale = 1.0 / math.sqrt(d) if scale is None else float(scale)
+    if (use_hip(q, k_cache, v_cache) and d in _DECODE_D and q.dtype in (torch.bfloat16, torch.float16, torch.float32)
+            and q.dim() == 4 and q.shape[1] >= 1 and _cache_layout_ok(k_cache) and _cache_layout_ok(v_cache)):
+        max_len = k_cache.shape[2]
+        bound = max_len if max_kv_len is None else min(int(max_kv_len), max_len)
+        if kv_len.dtype != torch.int32:
+            kv_len = kv_len.to(torch.int32)
+        return ops().fa_decode_chunk(q, k_cache, v_cache, kv_len.contiguous(), scale, bound, int(splits))
+    return decode_attention_chunk_ref(q, k_cache, v_cache, kv_len, scale)
+
+
+def kv_append_rope_chunk(qkv, cos, sin, pos, k_cache, v_cache):
+    d = k_cache.shape[-1]
+    es = qkv.element_size()
+    if (use_hip(qkv, k_cache, v_cache) and d % 8 == 0 and 8 <= d <= 256
+            and qkv.dtype in (torch.bfloat16, torch.float16, torch.float32) and qkv.dim() == 3 and qkv.shape[1] >= 1
+            and qkv.stride(-1) == 1 and qkv.data_ptr() % 16 == 0
+            and (qkv.stride(0) * es) % 16 == 0 and (qkv.stride(1) * es) % 16 == 0
+            and _cache_layout_ok(k_cache) and _cache_layout_ok(v_cache)):
+        if pos.dtype != torch.int32:
+            pos = pos.to(torch.int32)
+        return ops().kv_append_rope_chunk(qkv, cos.float().contiguous(), sin.float().contiguous(), pos.contiguous(),
+                                          k_cache, v_cache)
+    return kv_append_rope_chunk_ref(qkv, cos, sin, pos, k_cache, v_cache)

@@ -1475,6 +1475,121 @@ at::Tensor kv_append_rope(const at::Tensor& qkv, const at::Tensor& cos, const at
 }
 
 // ------------------------------------------------------------------------------------------
+// Multi-token decode attention / append of a chunk (csrc/flash_attn/fa_decode_chunk.hip)
+// ------------------------------------------------------------------------------------------
+std::tuple<at::Tensor, at::Tensor> fa_decode_chunk(const at::Tensor& q, const at::Tensor& k_cache,
+                                                   const at::Tensor& v_cache, const at::Tensor& kv_len, double scale,
+                                                   int64_t max_kv_len, int64_t splits) {
+  check_cuda(q, "q");
+  check_cache(k_cache, "k_cache");
+  check_cache(v_cache, "v_cache");
+  TORCH_CHECK(q.dim() == 4, "cs336: fa_decode_chunk q must be (B, n, H, D)");
+  const int64_t B = q.size(0), n = q.size(1), H = q.size(2), D = q.size(3), max_len = k_cache.size(2);
+  TORCH_CHECK(D == 32 || D == 64 || D == 80 || D == 128,
+              "cs336: fa_decode_chunk head dim must be 32, 64, 80 or 128 (got ", D, ")");
+  TORCH_CHECK(n >= 1, "cs336: fa_decode_chunk needs at least one query row");
+  TORCH_CHECK(q.scalar_type() == k_cache.scalar_type() && q.scalar_type() == v_cache.scalar_type(),
+              "cs336: q / k_cache / v_cache dtype mismatch");
+  TORCH_CHECK(k_cache.sizes() == v_cache.sizes() && k_cache.size(0) == B && k_cache.size(1) == H &&
+                  k_cache.size(3) == D,
+              "cs336: caches must be (B, H, max_len, D) matching q");
+  TORCH_CHECK(k_cache.device() == q.device() && v_cache.device() == q.device() && kv_len.device() == q.device(),
+              "cs336: fa_decode_chunk tensors must be on one device");
+  TORCH_CHECK(kv_len.scalar_type() == at::kInt && kv_len.dim() == 1 && kv_len.size(0) == B && kv_len.is_contiguous(),
+              "cs336: kv_len must be a contiguous int32 (B,) device tensor");
+  TORCH_CHECK(max_kv_len >= 0 && max_kv_len <= max_len, "cs336: max_kv_len must be in [0, max_len]");
+  TORCH_CHECK(splits >= 0 && splits <= 64, "cs336: splits must be in [0, 64] (0 = choose)");
+  TORCH_CHECK(n < ((int64_t)1 << 31), "cs336: fa_decode_chunk n must fit 32 bits");
+  const int64_t QT = cs336::fa_decode_chunk_qt((int)n), qtiles = (n + QT - 1) / QT;
+  // both grids in 32 bits: (b, h, query tile, split) workgroups and one merge workgroup per output row
+  TORCH_CHECK(B * H < ((int64_t)1 << 31) && B * H * qtiles < ((int64_t)1 << 31) / 64 && B * n * H < ((int64_t)1 << 31),
+              "cs336: fa_decode_chunk grid too large");
+  const DType t = to_dtype(q);
+  c10::DeviceGuard g(q.device());
+  const at::Tensor qc = q.contiguous();
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(qc.data_ptr()) % 16) == 0, "cs336: q must be 16-byte aligned");
+  at::Tensor o = at::empty({B, n, H, D}, q.options());
+  at::Tensor lse = at::empty({B, n, H}, q.options().dtype(at::kFloat));
+  if (B * H == 0) return {o, lse};
+  cs336::DecodeChunkParams p;
+  p.q = qc.data_ptr();
+  p.k = k_cache.data_ptr();
+  p.v = v_cache.data_ptr();
+  p.o = o.data_ptr();
+  p.lse = lse.data_ptr<float>();
+  p.kv_len = kv_len.data_ptr<int>();
+  p.k_sb = k_cache.stride(0); p.k_sh = k_cache.stride(1); p.k_sn = k_cache.stride(2);
+  p.v_sb = v_cache.stride(0); p.v_sh = v_cache.stride(1); p.v_sn = v_cache.stride(2);
+  p.B = (int)B; p.n = (int)n; p.H = (int)H; p.D = (int)D; p.max_len = (int)max_len;
+  p.scale = (float)scale;
+  // fa_decode's heuristic over the (batch, head, query tile) rows that share the CUs
+  p.splits = splits > 0 ? (int)splits : cs336::fa_decode_splits((int)(B * qtiles), (int)H, (int)D, t, (int)max_kv_len);
+  at::Tensor ws;
+  if (p.splits > 1) {
+    ws = at::empty({(int64_t)p.splits * B * n * H * (D + 1)}, q.options().dtype(at::kFloat));
+    p.opart = ws.data_ptr<float>();
+    p.lpart = p.opart + (int64_t)p.splits * B * n * H * D;
+  }
+  cs336::fa_decode_chunk(p, t, stream());
+  return {o, lse};
+}
+
+at::Tensor kv_append_rope_chunk(const at::Tensor& qkv, const at::Tensor& cos, const at::Tensor& sin,
+                                const at::Tensor& pos, at::Tensor& k_cache, at::Tensor& v_cache) {
+  check_cuda(qkv, "qkv");
+  check_cache(k_cache, "k_cache");
+  check_cache(v_cache, "v_cache");
+  TORCH_CHECK(qkv.dim() == 3 && qkv.stride(2) == 1, "cs336: qkv must be (B, n, 3*H*D) with a contiguous last dim");
+  const int64_t B = k_cache.size(0), H = k_cache.size(1), max_len = k_cache.size(2), D = k_cache.size(3);
+  const int64_t n = qkv.size(1);
+  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "cs336: k_cache / v_cache shape mismatch");
+  TORCH_CHECK(qkv.size(0) == B && qkv.size(2) == 3 * H * D,
+              "cs336: qkv must be (B, n, 3*H*D) for (B, H, max_len, D) caches");
+  TORCH_CHECK(D >= 8 && D <= 256 && D % 8 == 0,
+              "cs336: kv_append_rope_chunk head dim must be a multiple of 8 in [8, 256]");
+  TORCH_CHECK(qkv.scalar_type() == k_cache.scalar_type() && qkv.scalar_type() == v_cache.scalar_type(),
+              "cs336: qkv / k_cache / v_cache dtype mismatch");
+  const int64_t es = qkv.element_size();
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16) == 0 && (qkv.stride(0) * es) % 16 == 0 &&
+                  (qkv.stride(1) * es) % 16 == 0 && qkv.stride(0) >= 0 && qkv.stride(1) >= 0,
+              "cs336: qkv rows must be 16-byte aligned");
+  TORCH_CHECK(cos.is_cuda() && sin.is_cuda() && cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat &&
+                  cos.dim() == 2 && cos.is_contiguous() && sin.is_contiguous() && cos.sizes() == sin.sizes() &&
+                  cos.size(1) * 2 == D,
+              "cs336: rope cache must be contiguous fp32 (ctx, D/2)");
+  TORCH_CHECK(pos.scalar_type() == at::kInt && pos.dim() == 1 && pos.size(0) == B && pos.is_contiguous(),
+              "cs336: pos must be a contiguous int32 (B,) device tensor");
+  TORCH_CHECK(pos.device() == qkv.device() && cos.device() == qkv.device() && sin.device() == qkv.device() &&
+                  k_cache.device() == qkv.device() && v_cache.device() == qkv.device(),
+              "cs336: kv_append_rope_chunk tensors must be on one device");
+  TORCH_CHECK(n < ((int64_t)1 << 31) && B * 3 * H * (D / 8) < ((int64_t)1 << 31) &&
+                  B * n < ((int64_t)1 << 31) / (3 * H * (D / 8) > 0 ? 3 * H * (D / 8) : 1) &&
+                  cos.size(0) < ((int64_t)1 << 31),
+              "cs336: kv_append_rope_chunk too large for 32-bit indexing");
+  c10::DeviceGuard g(qkv.device());
+  at::Tensor q_out = at::empty({B, n, H, D}, qkv.options());
+  if (B * H * n == 0) return q_out;
+  cs336::AppendChunkParams p;
+  p.qkv = qkv.data_ptr();
+  p.qkv_sb = qkv.stride(0);
+  p.qkv_sn = qkv.stride(1);
+  p.cos = cos.data_ptr<float>();
+  p.sin = sin.data_ptr<float>();
+  p.pos = pos.data_ptr<int>();
+  p.q_out = q_out.data_ptr();
+  p.k = k_cache.data_ptr();
+  p.v = v_cache.data_ptr();
+  p.k_sb = k_cache.stride(0); p.k_sh = k_cache.stride(1); p.k_sn = k_cache.stride(2);
+  p.v_sb = v_cache.stride(0); p.v_sh = v_cache.stride(1); p.v_sn = v_cache.stride(2);
+  p.B = (int)B; p.n = (int)n; p.H = (int)H; p.D = (int)D; p.max_len = (int)max_len; p.ctx = (int)cos.size(0);
+  cs336::kv_append_rope_chunk(p, to_dtype(qkv), stream());
+  return q_out;
+}
+
+// the query tile fa_decode_chunk picks for n (benchmarks and profiles report it)
+int64_t fa_decode_chunk_qt(int64_t n) { return cs336::fa_decode_chunk_qt((int)std::min<int64_t>(n, 1 << 20)); }
+
+// ------------------------------------------------------------------------------------------
 // Skinny-M GEMM for decode (csrc/gemm/gemm_skinny.hip): out[M,N] = x[M,K] · w[N,K]ᵀ, M <= 16
 // ------------------------------------------------------------------------------------------
 bool gemm_skinny_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
@@ -1525,6 +1640,13 @@ TORCH_LIBRARY(cs336, m) {
   m.def("fa_last_launch() -> int[]", &fa_last_launch);
   m.def(
       "kv_append_rope(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor(a!) k_cache, Tensor(b!) v_cache) -> Tensor");
+  m.def(
+      "fa_decode_chunk(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_len, float scale, int max_kv_len, "
+      "int splits=0) -> (Tensor, Tensor)");
+  m.def(
+      "kv_append_rope_chunk(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor(a!) k_cache, Tensor(b!) v_cache) "
+      "-> Tensor");
+  m.def("fa_decode_chunk_qt(int n) -> int", &fa_decode_chunk_qt);
   m.def(
       "fa_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale, Tensor? rope_cos=None, Tensor? rope_sin=None, "
       "Tensor? rope_pos=None) -> (Tensor, Tensor)");
@@ -1589,6 +1711,8 @@ TORCH_LIBRARY_IMPL(cs336, CUDA, m) {
   m.impl("gemm_skinny", &gemm_skinny);
   m.impl("fa_decode", &fa_decode);
   m.impl("kv_append_rope", &kv_append_rope);
+  m.impl("fa_decode_chunk", &fa_decode_chunk);
+  m.impl("kv_append_rope_chunk", &kv_append_rope_chunk);
   m.impl("fa_fwd", &fa_fwd);
   m.impl("fa_fwd_ot", &fa_fwd_ot);
   m.impl("fa_bwd", &fa_bwd);

@@ -262,6 +262,48 @@ struct AppendParams {
 };
 void kv_append_rope(const AppendParams& p, DType t, hipStream_t s);
 
+// ---- multi-token decode attention over a KV cache (csrc/flash_attn/fa_decode_chunk.hip) ----
+// n query rows per (batch, head): query i of sequence b sees keys [0, kv_len[b] - (n - 1 - i)),
+// clamped to [0, max_len] (kv_len counts the chunk's own rows); a bound <= 0 gives o = 0, lse = -inf.
+struct DecodeChunkParams {
+  const void* q;  // (B, n, H, D) contiguous
+  const void* k;  // (B, H, max_len, D) views, as DecodeParams
+  const void* v;
+  void* o;            // (B, n, H, D) contiguous, q's dtype
+  float* lse;         // (B, n, H) natural-log LSE
+  const int* kv_len;  // (B,) device
+  int64_t k_sb, k_sh, k_sn;
+  int64_t v_sb, v_sh, v_sn;
+  int B, n, H, D, max_len;
+  float scale;
+  // splits > 1: fp32 partials opart (splits, B*n*H, D) / lpart (splits, B*n*H), merged by a second launch
+  int splits = 1;
+  float* opart = nullptr;
+  float* lpart = nullptr;
+};
+constexpr int kDecodeChunkQT = 8;  // most queries a workgroup owns (query tile)
+// the query tile the launcher picks for n: 1, 4 or 8; the grid has ceil(n / QT) query tiles
+int fa_decode_chunk_qt(int n);
+void fa_decode_chunk(const DecodeChunkParams& p, DType t, hipStream_t s);
+
+// n tokens per sequence: qkv (B, n, 3*H*D; q|k|v per token), token i rotated at position pos[b] + i;
+// rotated q -> q_out (B, n, H, D), rotated k and plain v -> cache row pos[b] + i. A token whose slot is
+// outside [0, min(max_len, ctx)) stores nothing (its q_out row is zeroed). D % 8 == 0.
+struct AppendChunkParams {
+  const void* qkv;
+  int64_t qkv_sb, qkv_sn;  // batch and token strides (elements)
+  const float* cos;        // (ctx, D/2) fp32
+  const float* sin;
+  const int* pos;  // (B,) device: slot of the chunk's first token
+  void* q_out;
+  void* k;
+  void* v;
+  int64_t k_sb, k_sh, k_sn;
+  int64_t v_sb, v_sh, v_sn;
+  int B, n, H, D, max_len, ctx;
+};
+void kv_append_rope_chunk(const AppendChunkParams& p, DType t, hipStream_t s);
+
 // ---- skinny-M GEMM for decode (csrc/gemm/gemm_skinny.hip) ----
 // out[M,N] = x[M,K] · w[N,K]ᵀ, 1 <= M <= 16, bf16 / fp16 with fp32 accumulation. Row strides in
 // elements; x / w rows 16-B aligned, K % 8 == 0, any N >= 1. Rows >= M, W rows >= N are never read.
