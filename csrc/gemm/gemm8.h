@@ -33,12 +33,19 @@ struct Args {
   int rseq, rope_cols, rdh;
   // diagnostic builds only (-DCS336_G8_STAMP, scripts/gemm8_stamps.py): per workgroup 8 uint64 --
   // s_memtime at start / after the prologue / after the main loop / after the epilogue's stores
-  // retired, s_memrealtime at start and end, HW_ID, XCC_ID. Ignored by the shipped build.
+  // retired, s_memrealtime at start and end, HW_ID, XCC_ID. Built with -DCS336_G8_STAMP=2 and with
+  // room for 5 rows per workgroup (stamp_rows), 4 more rows per workgroup follow those, laid out as
+  // gemm8w's below: per wave group and phase of the k-tile the cycles of reads + DMA issue + counted
+  // waits, of the wait at the barrier before the MFMA cluster and from there to the next barrier,
+  // summed over a few k-tiles in the middle of the range (scripts/gemm8_stamps.py --phases). Level
+  // 2 slows the loop; level 1 leaves it untouched. Ignored by the shipped build.
   uint64_t* stamps = nullptr;
+  int64_t stamp_rows = 0;
 };
 int pick_fn(int N, int epi, int half);
-// diagnostic: later launches with at most `blocks` workgroups write 8 stamps per workgroup into buf
-// (builds with -DCS336_G8_STAMP; returns false in other builds). blocks 0 = off.
+// diagnostic: later launches with at most `blocks` workgroups write 8 stamps per workgroup into buf,
+// and the per-phase rows too if it has 5 rows for each (builds with -DCS336_G8_STAMP; returns false
+// in other builds). blocks 0 = off.
 bool set_stamp_buffer(uint64_t* buf, int64_t blocks);
 bool launch(const Args& p, int epi, int fn, hipStream_t s);
 

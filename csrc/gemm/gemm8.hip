@@ -26,15 +26,39 @@
 // * two LDS stages (one K-tile each, ≤ 144 KiB) filled by LDS-DMA (buffer_load … lds, 16 B/lane),
 //   K-major images with the 16-B chunk XOR-swizzled by (row>>1)&7 (conflict-free ds_read_b128 for
 //   the 16x16x32 fragment lane groups; the swizzle goes on the per-lane global source address);
-// * each K-tile runs as 4 phases = the wave's 4 output quadrants (rows 0-63 / 64-127 × the first
-//   FB0 / last FN-FB0 column tiles). Phase = {ds_read its fragments; issue a slice of the K-tile
-//   after next; lgkmcnt(0); s_barrier; MFMA cluster; s_barrier}. The second wave group (waves 4-7,
-//   the partner of waves 0-3 on every SIMD) runs one barrier behind, so on each SIMD one wave
-//   multiplies while the other reads LDS / issues DMA;
-// * the K-tile after next is restaged into the stage just read as soon as the quadrant reads of its
-//   region retired (A rows 0-63 + first col tiles in phase 1, last col tiles in phase 2, A rows 64-127
-//   in phase 3), and one counted vmcnt per K-tile (phase 3) retires the next K-tile; DMA stays in
-//   flight across the raw s_barriers (never __syncthreads(), which would drain it);
+// * each K-tile runs as 2 phases split by rows: phase A = the wave's rows 0-63 × all FN column tiles
+//   (reads 8 A + 2·FN B fragments), phase B = rows 64-127 × all column tiles (re-reads the 8 A
+//   fragments into the same registers, keeps the B fragments: 72 operand VGPRs at FN 5), 8·FN MFMAs
+//   each. Phase = {issue a part of a later K-tile; ds_read its fragments; counted vmcnt;
+//   lgkmcnt(0); s_barrier; MFMA cluster; s_barrier}: four barriers per K-tile. The second wave
+//   group (waves 4-7, the partner of waves 0-3 on every SIMD) runs one barrier behind, so on each
+//   SIMD one wave multiplies while the other reads LDS / issues DMA. Every segment of the reader
+//   pays the LDS latency, the lgkmcnt(0) drain and the barrier once whatever it reads, so two
+//   segments of 18 / 8 reads against 640-cycle clusters cost less than four of 14 / 4 / 8 / 0
+//   against 384 / 256-cycle ones (profiles/gemm8_two_phase.md). Each accumulator still gets k-half
+//   0 then k-half 1 of each K-tile, K-tiles in order: results are bitwise those of the 4-phase loop;
+// * the fragment addresses live in four registers per lane (A / B × the two k-halves), every
+//   fragment is an immediate offset from one of them, and they change stage once per K-tile behind
+//   the last MFMAs: no VALU in the reader's segment;
+// * DMA order and counted waits. A K-tile's granules are restaged in two parts: X = A rows 0-63 of
+//   each wave-row group and all of B (G_X per wave; read in phase A only), Y = A rows 64-127 (G_Y;
+//   read in phase B only); G_X + G_Y = G_ALL. Per K-tile t (stage t & 1), in issue order:
+//     prologue  X(0) Y(0) X(1) Y(1), retires K-tile 0 whole: vmcnt(G_ALL), or vmcnt(0) with one K-tile;
+//     A(t)      issues Y(t+1) into the other stage (t >= 1; Y(1) came from the prologue) -- that
+//               region was last read in B(t-1); then retires Y(t), which B(t) reads: younger are
+//               X(t+1) [B(t-1) or the prologue] and Y(t+1) -> vmcnt(G_ALL); on the last K-tile
+//               nothing is younger -> vmcnt(0);
+//     B(t)      issues X(t+2) into this stage -- its reads retired in A(t); then retires X(t+1),
+//               which A(t+1) reads: younger are Y(t+1) [A(t) or the prologue] and X(t+2) ->
+//               vmcnt(G_ALL); with no K-tile t+2 only Y(t+1) -> vmcnt(G_Y); on the last K-tile no wait.
+//   So the issue order is … Y(t+1), X(t+2), Y(t+2), X(t+3) … and every part has one full K-tile
+//   (about 2800 cycles) in flight. The partial last K-tile of a K tail goes through the same points
+//   with its out-of-range lanes masked. RAW: every part is read one phase after the wait that
+//   retires it -- the wave's own vmcnt, then the barrier before the cluster, which the other wave
+//   group (one barrier away) passes after its own wait and before either group's first read. WAR:
+//   every restage comes one segment after the region's last reads, which both groups retired
+//   (lgkmcnt(0)) before the barrier that precedes the issuing segment. DMA stays in flight across
+//   the raw s_barriers (never __syncthreads(), which would drain it);
 // * XCD-aware bijective block remap + grouped tile order (8 tile-rows) for L2 reuse.
 #include "cs336/kernels.h"
 #include "gemm8.h"
@@ -79,7 +103,7 @@ template <int FN>
 struct Geo {
   static constexpr int BN = 64 * FN;           // tile columns
   static constexpr int WTN = 16 * FN;          // per-wave columns
-  static constexpr int FB0 = (FN + 1) / 2;     // column tiles of the first column quadrant
+  static constexpr int FB0 = (FN + 1) / 2;     // column tiles of a wave's first B restage slice
   static constexpr int B0C = 16 * FB0;         // its width
   static constexpr int A_BYTES = BM * 128;     // [256 rows][64 k] bf16
   static constexpr int B_BYTES = BN * 128;
@@ -91,6 +115,9 @@ struct Geo {
   static constexpr int G_A1 = 16 / 8;
   static constexpr int G_P1 = G_A0 + G_B0, G_P2 = G_B1, G_P3 = G_A1;
   static constexpr int G_ALL = G_P1 + G_P2 + G_P3;
+  // the two restage parts of the main loop: X = slices 1 and 2 (A rows 0-63 of each wave-row group
+  // and all of B: read in phase A only), Y = slice 3 (A rows 64-127: read in phase B only)
+  static constexpr int G_X = G_P1 + G_P2, G_Y = G_P3;
   static_assert((4 * B0C / 8) % 8 == 0 && (4 * (WTN - B0C) / 8) % 8 == 0, "B granules must split over 8 waves");
 };
 
@@ -100,7 +127,7 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(const Args p) {
   static_assert(!TAIL || EPI == 0, "tails: plain C = A·Bᵀ only");
   constexpr bool NTAIL = TAIL & 1, KTAIL = TAIL & 2;
   using G = Geo<FN>;
-  constexpr int BN = G::BN, WTN = G::WTN, FB0 = G::FB0, B0C = G::B0C, STAGE = G::STAGE;
+  constexpr int BN = G::BN, WTN = G::WTN, B0C = G::B0C, STAGE = G::STAGE;
   // the main loop's two stages, or (epilogue) the whole bf16 tile image
   __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE > BM * BN * 2 ? 2 * STAGE : BM * BN * 2];
 
@@ -196,8 +223,8 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(const Args p) {
     const int g = wave + 8 * (i - G::G_P1 - G::G_P2);
     return g < 8 ? 64 + 8 * g : 192 + 8 * (g - 8);
   };
-  // issue slice `part` (1: A0+B0, 2: B1, 3: A1; 0: all) of k-tile kt into stage st; `masked`: the
-  // partial last k-tile (lanes whose chunk lies at or past K read out of range = zeros)
+  // issue part `part` (1: X = A0+B0+B1, 2: Y = A1; 0: all, X then Y) of k-tile kt into stage st;
+  // `masked`: the partial last k-tile (lanes whose chunk lies at or past K read out of range = zeros)
   auto issue_v = [&](int part, int kt, int st, bool masked) {
     const uint32_t so = (uint32_t)kt * (BK * 2), base = (uint32_t)(st * STAGE);
     auto vo = [&](int i) -> uint32_t {
@@ -209,15 +236,11 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(const Args p) {
 #pragma unroll
       for (int i = 0; i < G::G_A0; ++i) glds(ra, vo(i), so, base + ldso[i]);
 #pragma unroll
-      for (int i = G::G_A0; i < G::G_P1; ++i) glds(rb, vo(i), so, base + ldso[i]);
+      for (int i = G::G_A0; i < G::G_X; ++i) glds(rb, vo(i), so, base + ldso[i]);
     }
     if (part == 0 || part == 2) {
 #pragma unroll
-      for (int i = G::G_P1; i < G::G_P1 + G::G_P2; ++i) glds(rb, vo(i), so, base + ldso[i]);
-    }
-    if (part == 0 || part == 3) {
-#pragma unroll
-      for (int i = G::G_P1 + G::G_P2; i < G::G_ALL; ++i) glds(ra, vo(i), so, base + ldso[i]);
+      for (int i = G::G_X; i < G::G_ALL; ++i) glds(ra, vo(i), so, base + ldso[i]);
     }
   };
   auto issue = [&](int part, int kt, int st) {
@@ -226,12 +249,32 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(const Args p) {
   };
 
   // ---- fragment reads: lane row (l&15), 16-B chunk 4·ks + (l>>4) XOR ((l&15)>>1) -----------
+  // Each lane carries four LDS byte addresses -- the wave's first A row and first B row of this
+  // k-tile's stage, for k-half 0 and 1 -- and reaches every fragment by an immediate offset (16 rows
+  // = 2 KiB apart); they change stage once per k-tile behind the last MFMAs (next_stage), so the
+  // reader's segment, the side the partner's cluster waits for, holds no VALU
   const int x = (lane & 15) >> 1, q4 = lane >> 4;
-  const uint32_t lo0 = (uint32_t)((lane & 15) * 128 + ((q4 ^ x) * 16));
-  const uint32_t lo1 = (uint32_t)((lane & 15) * 128 + (((4 + q4) ^ x) * 16));
-  auto frag = [&](uint32_t img_off, int row0, int ks) -> bf16x8 {
-    const char* ptr = smem + img_off + row0 * 128 + (ks ? lo1 : lo0);
-    return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(ptr));
+  const int arow = wr * 128, bcol = wc * WTN;
+  uint32_t ada[2], adb[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    const uint32_t lo = (uint32_t)((lane & 15) * 128 + (((4 * ks + q4) ^ x) * 16));
+    ada[ks] = lo + (uint32_t)(arow * 128);
+    adb[ks] = lo + (uint32_t)(G::A_BYTES + bcol * 128);
+  }
+  auto frag = [&](uint32_t addr, int row0) -> bf16x8 {
+    return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(smem + addr + row0 * 128));
+  };
+  // opaque to the compiler so that the adds stay where they are put
+  auto next_stage = [&](int t) {
+    const uint32_t d = (t & 1) ? (uint32_t)(-STAGE) : (uint32_t)STAGE;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      ada[ks] += d;
+      asm volatile("" : "+v"(ada[ks]));
+      adb[ks] += d;
+      asm volatile("" : "+v"(adb[ks]));
+    }
   };
 
   f32x4 acc[8][FN];
@@ -240,22 +283,49 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(const Args p) {
 #pragma unroll
     for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  bf16x8 fa[4][2], fb0[FB0][2], fb1[FN - FB0 > 0 ? FN - FB0 : 1][2];
-  const int arow = wr * 128, bcol = wc * WTN;
+  bf16x8 fa[4][2], fb[FN][2];  // one 64-row half of the wave's A rows (re-read per phase), all of its B
 
-  auto mma = [&](int i0, const bf16x8 (&a)[4][2], auto& bq, int j0, int nj) {
+  // one phase's MFMA cluster: 4 row blocks (from i0) x FN column blocks, k-half 0 then k-half 1
+  auto mma = [&](int i0) {
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < nj; ++j)
+        for (int j = 0; j < FN; ++j)
           // B fragment as the MFMA's A operand: D = (A·Bᵀ)ᵀ per 16x16 block, so lane l holds
           // C[m = l&15][n = 4(l>>4) + r] -- four consecutive output columns (one 8/16-B LDS write)
-          acc[i0 + i][j0 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq[j][ks], a[i][ks], acc[i0 + i][j0 + j], 0, 0, 0);
+          acc[i0 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j][ks], fa[i][ks], acc[i0 + i][j], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
   };
+
+#if CS336_G8_STAMP >= 2
+  // -DCS336_G8_STAMP=2, stamp buffer with room for the per-phase rows (5 rows per workgroup): kStampTiles
+  // k-tiles in the middle of the range are stamped at every phase's entry (3p), after its reads / DMA
+  // issue / waits (3p + 1) and after the barrier before its MFMA cluster (3p + 2); 3 kPhases = after
+  // the last barrier. Sums of the three segments per phase and wave group leave through the stamp
+  // buffer (scripts/gemm8_stamps.py --phases; the rows have room for four phases)
+  constexpr int kStampTiles = 4, kPhases = 2;
+  const bool st_ph = p.stamps && p.stamp_rows >= 5 * (int64_t)gridDim.x;
+  const int s_lo = nkt > kStampTiles ? (nkt - kStampTiles) / 2 : 0;
+  uint32_t s_work[4] = {0, 0, 0, 0}, s_wait[4] = {0, 0, 0, 0}, s_mma[4] = {0, 0, 0, 0}, s_cnt = 0;
+  auto stamp = [&]() -> uint32_t {
+    uint64_t v;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v)::"memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return (uint32_t)v;
+  };
+#define CS336_G8_PSTAMP(I) \
+  do {                     \
+    if (samp) ts_[I] = stamp(); \
+  } while (0)
+#else
+#define CS336_G8_PSTAMP(I) \
+  do {                     \
+  } while (0)
+#endif
 
   // ---- prologue: k-tiles 0 and 1 -------------------------------------------------------------
   issue(0, 0, 0);
@@ -272,58 +342,85 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(const Args p) {
   if (wr == 1) sbarrier();  // second wave group one barrier behind (SIMD partners offset)
 
   for (int t = 0; t < nkt; ++t) {
-    const uint32_t st = (uint32_t)((t & 1) * STAGE);
-    const bool pre = t + 2 < nkt;  // the k-tile after next exists: restage this stage with it
-    // P0: quadrant (rows 0-63, first col tiles)
+    const bool more1 = t + 1 < nkt, more2 = t + 2 < nkt;  // k-tile t+1 / t+2 exists
+#if CS336_G8_STAMP >= 2
+    const bool samp = st_ph && t >= s_lo && t < s_lo + kStampTiles;
+    uint32_t ts_[3 * kPhases + 1] = {};
+#endif
+    // Phase A: rows 0-63 x all column tiles. Restage the other stage's Y region (last read in phase
+    // B of k-tile t-1) with k-tile t+1 -- k-tile 1 came whole from the prologue; retire Y(t), which
+    // phase B reads
+    CS336_G8_PSTAMP(0);
+    if (t > 0 && more1) issue(2, t + 1, (t + 1) & 1);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) fa[i][ks] = frag(st, arow + 16 * i, ks);
+      for (int ks = 0; ks < 2; ++ks) fa[i][ks] = frag(ada[ks], 16 * i);
 #pragma unroll
-    for (int j = 0; j < FB0; ++j)
+    for (int j = 0; j < FN; ++j)
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) fb0[j][ks] = frag(st + G::A_BYTES, bcol + 16 * j, ks);
+      for (int ks = 0; ks < 2; ++ks) fb[j][ks] = frag(adb[ks], 16 * j);
+    if (more1) vmcnt<G::G_ALL>();  // younger: X(t+1), Y(t+1)
+    else vmcnt<0>();
     lgkm0();
+    CS336_G8_PSTAMP(1);
     sbarrier();
-    mma(0, fa, fb0, 0, FB0);
+    CS336_G8_PSTAMP(2);
+    mma(0);
     sbarrier();
-    // P1: quadrant (rows 0-63, last col tiles); restage A rows 0-63 / B first cols with t+2
-    if constexpr (FN - FB0 > 0) {
-#pragma unroll
-      for (int j = 0; j < FN - FB0; ++j)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) fb1[j][ks] = frag(st + G::A_BYTES, bcol + B0C + 16 * j, ks);
-    }
-    if (pre) issue(1, t + 2, t & 1);
-    lgkm0();
-    sbarrier();
-    if constexpr (FN - FB0 > 0) mma(0, fa, fb1, FB0, FN - FB0);
-    sbarrier();
-    // P2: quadrant (rows 64-127, last col tiles); restage B last cols
+    CS336_G8_PSTAMP(3);
+    // Phase B: rows 64-127 x all column tiles (B fragments kept). Restage this stage's X region (its
+    // reads retired in phase A) with k-tile t+2; retire X(t+1), which phase A of k-tile t+1 reads
+    if (more2) issue(1, t + 2, t & 1);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) fa[i][ks] = frag(st, arow + 64 + 16 * i, ks);
-    if (pre) issue(2, t + 2, t & 1);
+      for (int ks = 0; ks < 2; ++ks) fa[i][ks] = frag(ada[ks], 64 + 16 * i);
+    if (more2) vmcnt<G::G_ALL>();      // younger: Y(t+1), X(t+2)
+    else if (more1) vmcnt<G::G_Y>();   // younger: Y(t+1)
     lgkm0();
+    CS336_G8_PSTAMP(4);
     sbarrier();
-    if constexpr (FN - FB0 > 0) mma(4, fa, fb1, FB0, FN - FB0);
+    CS336_G8_PSTAMP(5);
+    mma(4);
+    next_stage(t);
     sbarrier();
-    // P3: quadrant (rows 64-127, first col tiles); retire k-tile t+1, restage A rows 64-127
-    if (t + 1 < nkt) {
-      if (pre) vmcnt<G::G_P1 + G::G_P2>();
-      else vmcnt<0>();
+    CS336_G8_PSTAMP(6);
+#if CS336_G8_STAMP >= 2
+    if (samp) {
+#pragma unroll
+      for (int ph = 0; ph < kPhases; ++ph) {
+        s_work[ph] += ts_[3 * ph + 1] - ts_[3 * ph];
+        s_wait[ph] += ts_[3 * ph + 2] - ts_[3 * ph + 1];
+        s_mma[ph] += ts_[3 * ph + 3] - ts_[3 * ph + 2];
+      }
+      ++s_cnt;
     }
-    if (pre) issue(3, t + 2, t & 1);
-    sbarrier();
-    mma(4, fa, fb0, 0, FB0);
-    sbarrier();
+#endif
   }
+#undef CS336_G8_PSTAMP
   if (wr == 0) sbarrier();  // balance the wave-group offset
   lgkm0();
   sbarrier();
 #ifdef CS336_G8_STAMP
   st_t2 = __builtin_amdgcn_s_memtime();
+#endif
+#if CS336_G8_STAMP >= 2
+  // per-phase rows behind the workgroups' own rows, 4 rows of 8 per workgroup: wave group g -> rows
+  // 2g (work[4], wait[4]) and 2g + 1 (mma[4], stamped k-tiles, k-tiles, HW_ID, XCC_ID)
+  if (st_ph && lane == 0 && wc == 0) {
+    uint32_t hw, xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    uint64_t* o = p.stamps + 8 * (int64_t)gridDim.x + 32 * (int64_t)blockIdx.x + 16 * wr;
+#pragma unroll
+    for (int ph = 0; ph < kPhases; ++ph) {
+      o[ph] = s_work[ph];
+      o[4 + ph] = s_wait[ph];
+      o[8 + ph] = s_mma[ph];
+    }
+    o[12] = s_cnt; o[13] = (uint64_t)nkt; o[14] = hw; o[15] = xcc;
+  }
 #endif
 
   // ---- epilogue ----------------------------------------------------------------------------
@@ -544,7 +641,10 @@ void launch_t(const Args& p_in, hipStream_t s) {
   const int tail = EPI == 0 ? (p.N % BN != 0 ? 1 : 0) | (p.K % BK != 0 ? 2 : 0) : 0;
   const int tiles_n = (tail & 1) ? (p.N + BN - 1) / BN : p.N / BN;
   const dim3 grid((unsigned)((p.M / BM) * tiles_n)), block(NT);
-  if (g_stamps && (int64_t)grid.x <= g_stamp_blocks) p.stamps = g_stamps;
+  if (g_stamps && (int64_t)grid.x <= g_stamp_blocks) {
+    p.stamps = g_stamps;
+    p.stamp_rows = g_stamp_blocks;
+  }
   if constexpr (EPI == 0) {
     if (tail == 1) {
       hipLaunchKernelGGL((gemm8_kernel<FN, 0, 1>), grid, block, 0, s, p);

@@ -10,6 +10,16 @@ waits for them, the shipped one does not), plus its CU (HW_ID, XCC_ID). Reported
 shader cycles (median over workgroups): prologue, main loop, epilogue, and per CU the gap between
 one workgroup's end and the next one's start on that CU (dispatch + launch overhead), plus the
 clock (memtime ticks per memrealtime tick x 100 MHz) and each phase's share of the busy span.
+
+``--phases`` looks inside the main loop instead (build the variant with ``-DCS336_G8_STAMP=2``: the
+stamp points inside the loop slow it down, so level 1 leaves them out and the whole-tile figures
+above are taken on a level-1 build): the stamp buffer gets room for the per-phase rows, and four
+k-tiles in the middle of every workgroup's range are stamped at each phase's entry, after
+its reads / DMA issue / waits and after the barrier before its MFMA cluster (two phases per k-tile:
+A = rows 0-63, B = rows 64-127 of the wave). Reported per wave group as cycles per k-tile, median
+over workgroups: work / wait / mma per phase, read as in scripts/gemm8w_stamps.py (`work` longer
+than the partner's cluster shows as that phase's `wait` near zero and the partner's `mma`
+stretched). Each stamp costs about 40 cycles, so compare segments, not the k-tile total.
 """
 
 from __future__ import annotations
@@ -23,6 +33,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from gemm8w_stamps import analyse as analyse_phases  # noqa: E402  (same row layout)
 
 # name, N, K, epi (M = tokens), per model
 PROBLEMS = {
@@ -79,6 +90,7 @@ def main():
     ap.add_argument("--tokens", type=int, default=52224)
     ap.add_argument("--model", choices=sorted(PROBLEMS), default="xl")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--phases", action="store_true", help="per-phase work / wait / mma inside the k-tile")
     args = ap.parse_args()
     from cs336_systems import ops
 
@@ -95,7 +107,7 @@ def main():
         h = torch.empty(M, half, device="cuda", dtype=torch.bfloat16) if epi == 1 else None
         y = ((torch.rand(M, 2 * N, device="cuda", generator=g) * 2 - 1) * 3).bfloat16() if epi == 2 else None
         blocks = (M // 256) * (N // 320)
-        st = torch.zeros(blocks, 8, dtype=torch.int64, device="cuda")
+        st = torch.zeros(5 * blocks if args.phases else blocks, 8, dtype=torch.int64, device="cuda")
         for _ in range(3):
             cs.gemm8(a, b, c, epi, 5, h, y, half)
         torch.cuda.synchronize()
@@ -107,7 +119,12 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         cs.gemm8_stamps(None)
-        row = {"model": args.model, "problem": name, "M": M, "N": N, "K": K, "epi": epi, "ms": round(e0.elapsed_time(e1), 4), **analyse(st)}
+        row = {"model": args.model, "problem": name, "M": M, "N": N, "K": K, "epi": epi, "ms": round(e0.elapsed_time(e1), 4)}
+        if args.phases:
+            tile = analyse(st[:blocks])
+            row.update(main_cyc=tile["main_cyc"], clock_ghz=tile["clock_ghz"], **analyse_phases(st[blocks:].view(blocks, 4, 8)))
+        else:
+            row.update(analyse(st))
         rows.append(row)
         print(json.dumps(row), flush=True)
         del a, b, c, h, y, st

@@ -49,6 +49,11 @@ for r in json.load(open('gpurun_out/flash4096.json')):
       CS336_LIB=cs336_systems/_native/variants/base/libcs336_hip.so timeout -k 10 240 python -u scripts/gemm8w_bitwise.py dump "$dump" 2>&1 && \
       timeout -k 10 240 python -u scripts/gemm8w_bitwise.py check "$dump" 2>&1 || { rm -f "$dump"; exit 1; }
       rm -f "$dump" ;;
+    g8bits)  # gemm8 on the XL problems of every epilogue kind and the vocabulary head, base variant lib vs this tree's lib, bit for bit
+      dump=$(mktemp --suffix .pt)
+      CS336_LIB=cs336_systems/_native/variants/base/libcs336_hip.so timeout -k 10 240 python -u scripts/gemm8_bitwise.py dump "$dump" 2>&1 && \
+      timeout -k 10 240 python -u scripts/gemm8_bitwise.py check "$dump" 2>&1 || { rm -f "$dump"; exit 1; }
+      rm -f "$dump" ;;
     graphab)  # eager step vs the whole step captured in one HIP graph, same box
       timeout -k 10 900 python scripts/ab.py bench "eager:" "graphs:PYTHONFAULTHANDLER=1:--graphs on" --rounds ${AB_ROUNDS:-2} --steps 10 --timeout 300 > gpurun_out/graphab.log 2>&1 || { tail -30 gpurun_out/graphab.log; exit 1; }
       tail -8 gpurun_out/graphab.log ;;
