@@ -1166,20 +1166,24 @@ bool gemm8_ok(int64_t M, int64_t N, int64_t K, int64_t epi, int64_t half) {
 }
 
 // gemm8 / gemm8w address each operand through one buffer descriptor with 32-bit byte offsets
-constexpr int64_t kDmaLimit = (int64_t(1) << 31) - (int64_t(1) << 20);
+using cs336::gemm8::kDmaLimit;
 bool gemm8_extents_ok(const at::Tensor& a, const at::Tensor& b) {
   const int64_t K = a.size(1);
   return (255 * a.stride(0) + K) * 2 < kDmaLimit && ((b.size(0) - 1) * b.stride(0) + K) * 2 < kDmaLimit;
 }
 
-void gemm8(const at::Tensor& a, const at::Tensor& b, at::Tensor& c, int64_t epi, int64_t fn, const OptT& h,
-           const OptT& y, int64_t half) {
+// diagnostic stamp buffer of gemm8 and gemm8w (CS336_G8_STAMP builds): every launch gets it in its
+// Args / WArgs and drops it if its grid needs more rows
+uint64_t* g_stamp_buf = nullptr;
+int64_t g_stamp_rows = 0;
+
+// Checks a and b and fills the Args fields every gemm8 op shares: operands, strides, sizes, stamp
+// buffer. Each op checks c itself, at the place and under the name its order of errors needs, and
+// only then reads its pointer and stride.
+cs336::gemm8::Args gemm8_args(const at::Tensor& a, const at::Tensor& b) {
   const int64_t M = a.size(0), K = a.size(1), N = b.size(0);
   gemm8_check(a, M, K, "a");
   gemm8_check(b, N, K, "b");
-  TORCH_CHECK(epi >= 0 && epi <= 2, "cs336: gemm8 epi");
-  TORCH_CHECK(gemm8_ok(M, N, K, epi, half), "cs336: gemm8 does not take M=", M, " N=", N, " K=", K, " epi=", epi);
-  TORCH_CHECK(gemm8_extents_ok(a, b), "cs336: gemm8 operand extent exceeds the 2 GiB DMA range");
   cs336::gemm8::Args p{};
   p.a = reinterpret_cast<const uint16_t*>(a.data_ptr());
   p.b = reinterpret_cast<const uint16_t*>(b.data_ptr());
@@ -1188,6 +1192,18 @@ void gemm8(const at::Tensor& a, const at::Tensor& b, at::Tensor& c, int64_t epi,
   p.M = (int)M;
   p.N = (int)N;
   p.K = (int)K;
+  p.stamps = g_stamp_buf;
+  p.stamp_rows = g_stamp_rows;
+  return p;
+}
+
+void gemm8(const at::Tensor& a, const at::Tensor& b, at::Tensor& c, int64_t epi, int64_t fn, const OptT& h,
+           const OptT& y, int64_t half) {
+  const int64_t M = a.size(0), K = a.size(1), N = b.size(0);
+  cs336::gemm8::Args p = gemm8_args(a, b);
+  TORCH_CHECK(epi >= 0 && epi <= 2, "cs336: gemm8 epi");
+  TORCH_CHECK(gemm8_ok(M, N, K, epi, half), "cs336: gemm8 does not take M=", M, " N=", N, " K=", K, " epi=", epi);
+  TORCH_CHECK(gemm8_extents_ok(a, b), "cs336: gemm8 operand extent exceeds the 2 GiB DMA range");
   p.half = (int)half;
   if (epi == 0) {
     gemm8_check(c, M, N, "c");
@@ -1212,21 +1228,19 @@ void gemm8(const at::Tensor& a, const at::Tensor& b, at::Tensor& c, int64_t epi,
   TORCH_CHECK(cs336::gemm8::launch(p, (int)epi, (int)fn, stream()), "cs336: gemm8 launch (fn ", fn, ")");
 }
 
-// diagnostic stamp buffer of gemm8 (CS336_G8_STAMP builds, scripts/gemm8_stamps.py): uint64 (blocks, 8)
-// or None = off; returns whether this build writes stamps
-// gemm8w writes 4 such rows per workgroup into the same buffer (scripts/gemm8w_stamps.py)
-uint64_t* g_stamp_buf = nullptr;
-int64_t g_stamp_rows = 0;
+// sets the diagnostic stamp buffer (scripts/gemm8_stamps.py, scripts/gemm8w_stamps.py): int64 (rows, 8)
+// or None = off; returns whether this build writes stamps. gemm8 writes one row per workgroup, and
+// 4 more behind those if there are 5 per workgroup; gemm8w writes 4 rows per workgroup
 bool gemm8_stamps(const std::optional<at::Tensor>& buf) {
   g_stamp_buf = nullptr;
   g_stamp_rows = 0;
-  if (!buf.has_value()) return cs336::gemm8::set_stamp_buffer(nullptr, 0);
+  if (!buf.has_value()) return cs336::gemm8::stamps_built();
   const at::Tensor& b = *buf;
   TORCH_CHECK(b.is_cuda() && b.scalar_type() == at::kLong && b.is_contiguous() && b.dim() == 2 && b.size(1) == 8,
               "cs336: gemm8 stamp buffer must be a contiguous int64 (blocks, 8) GPU tensor");
   g_stamp_buf = reinterpret_cast<uint64_t*>(b.data_ptr<int64_t>());
   g_stamp_rows = b.size(0);
-  return cs336::gemm8::set_stamp_buffer(g_stamp_buf, g_stamp_rows);
+  return cs336::gemm8::stamps_built();
 }
 
 // QKV projection forward with RoPE in the store (gemm8 epi 3): c = a @ b.T with columns < rope_cols
@@ -1234,9 +1248,10 @@ bool gemm8_stamps(const std::optional<at::Tensor>& buf) {
 void gemm8_rope(const at::Tensor& a, const at::Tensor& b, at::Tensor& c, const at::Tensor& cos, const at::Tensor& sin,
                 const OptT& pos, int64_t seq, int64_t rope_cols, int64_t dhead) {
   const int64_t M = a.size(0), K = a.size(1), N = b.size(0);
-  gemm8_check(a, M, K, "a");
-  gemm8_check(b, N, K, "b");
+  cs336::gemm8::Args p = gemm8_args(a, b);
   gemm8_check(c, M, N, "c");
+  p.c = reinterpret_cast<uint16_t*>(c.data_ptr());
+  p.ldc = c.stride(0);
   TORCH_CHECK(gemm8_ok(M, N, K, 3, rope_cols), "cs336: gemm8_rope does not take M=", M, " N=", N, " K=", K,
               " rope_cols=", rope_cols);
   TORCH_CHECK(gemm8_extents_ok(a, b), "cs336: gemm8_rope operand extent exceeds the 2 GiB DMA range");
@@ -1254,16 +1269,6 @@ void gemm8_rope(const at::Tensor& a, const at::Tensor& b, at::Tensor& c, const a
   } else {
     TORCH_CHECK(seq <= cos.size(0), "cs336: gemm8_rope seq ", seq, " exceeds the RoPE cache ", cos.size(0));
   }
-  cs336::gemm8::Args p{};
-  p.a = reinterpret_cast<const uint16_t*>(a.data_ptr());
-  p.b = reinterpret_cast<const uint16_t*>(b.data_ptr());
-  p.c = reinterpret_cast<uint16_t*>(c.data_ptr());
-  p.lda = a.stride(0);
-  p.ldb = b.stride(0);
-  p.ldc = c.stride(0);
-  p.M = (int)M;
-  p.N = (int)N;
-  p.K = (int)K;
   p.rcos = cos.data_ptr<float>();
   p.rsin = sin.data_ptr<float>();
   p.rpos = pp;

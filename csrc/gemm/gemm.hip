@@ -28,13 +28,14 @@
 // * XCD-aware bijective block remap, then grouped tile order (8 tile-rows per group) so the tiles
 //   co-resident on one XCD share A row-panels and B column-panels in that XCD's L2.
 #include "cs336/kernels.h"
+#include "gemm_common.h"
 
 namespace cs336 {
 namespace gemm {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+using namespace gemm_common;
+
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
@@ -49,14 +50,6 @@ constexpr int kBK = 64;
 #ifndef CS336_GEMM_PRIO
 #define CS336_GEMM_PRIO 0
 #endif
-constexpr int kGroupM = 8;
-
-__device__ __forceinline__ int xcd_remap(int bid, int total) {
-  const int xcd = bid & 7, q = total >> 3, r = total & 7;
-  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + (bid >> 3);
-}
-
 // ---- swizzles ---------------------------------------------------------------------------------
 // K-major image: row r (128 B = 8 chunks of 8 bf16); physical chunk = logical ^ ((r>>1)&7)
 __device__ __forceinline__ int kswz(int r) { return (r >> 1) & 7; }
@@ -152,10 +145,6 @@ __device__ __forceinline__ bf16x8 frag_mn(const char* img, int col0, int ks, int
   return __builtin_bit_cast(bf16x8, v);
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 __device__ __forceinline__ void barrier() { asm volatile("s_barrier" ::: "memory"); }
 
 // round-to-nearest-even via v_cvt_pk_bf16_f32 (keeps NaN a NaN, unlike the integer trick)
@@ -181,12 +170,8 @@ __global__ __launch_bounds__(WGM* WGN * 64, 1) void gemm_kernel(const GemmArgs p
 
   // tile coordinates: XCD remap, then grouped order
   const int tiles_n = p.N / BN, tiles_m = p.M / BM;
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int per_group = kGroupM * tiles_n;
-  const int first_m = (bid / per_group) * kGroupM;
-  const int gsz = min(tiles_m - first_m, kGroupM);
-  const int tm = first_m + (bid % per_group) % gsz, tn = (bid % per_group) / gsz;
-  const int m0 = tm * BM, n0 = tn * BN;
+  const Tile tile = tile_of_block(blockIdx.x, gridDim.x, tiles_m, tiles_n);
+  const int m0 = tile.tm * BM, n0 = tile.tn * BN;
 
   // k-tile range of this split
   const int nkt_all = p.K / kBK, split = blockIdx.y, nsplit = gridDim.y;
@@ -210,9 +195,9 @@ __global__ __launch_bounds__(WGM* WGN * 64, 1) void gemm_kernel(const GemmArgs p
   };
   // own loads of the oldest outstanding tile retired, one younger tile may stay in flight
   auto wait_one_in_flight = [&]() {
-    if (extra == 0) wait_vm<LF>();
-    else if (extra == 1) wait_vm<LF + 1>();
-    else wait_vm<LF + 2>();
+    if (extra == 0) vmcnt<LF>();
+    else if (extra == 1) vmcnt<LF + 1>();
+    else vmcnt<LF + 2>();
   };
 
   f32x4 acc[FM][FN];
@@ -243,9 +228,9 @@ __global__ __launch_bounds__(WGM* WGN * 64, 1) void gemm_kernel(const GemmArgs p
   // the wait that retires tile t (loads of t+1 may stay in flight) + the barrier that publishes it
   auto land = [&](int t) {
     if (NS == 3 && t + 1 < nkt) wait_one_in_flight();
-    else wait_vm<0>();
+    else vmcnt<0>();
     // this wave's reads of the slot about to be restaged have returned (WAR across the barrier)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lgkm0();
     barrier();
   };
 
@@ -320,7 +305,7 @@ __global__ __launch_bounds__(WGM* WGN * 64, 1) void gemm_kernel(const GemmArgs p
     constexpr int RB = WTN * ES, CPR = RB / 16, NCH = 16 * CPR;  // row bytes, chunks per row / block
     static_assert(RB % 16 == 0, "wave tile row must be whole 16-B chunks");
     static_assert(NW * 16 * RB <= NS * STAGE, "epilogue scratch exceeds the LDS ring");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lgkm0();
     barrier();  // every wave's last fragment reads of the ring are done
     char* scr = smem + wave * 16 * RB;
     const int r0 = m0 + wm * WTM, c0 = n0 + wn * WTN;

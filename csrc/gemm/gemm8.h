@@ -38,15 +38,19 @@ struct Args {
   // gemm8w's below: per wave group and phase of the k-tile the cycles of reads + DMA issue + counted
   // waits, of the wait at the barrier before the MFMA cluster and from there to the next barrier,
   // summed over a few k-tiles in the middle of the range (scripts/gemm8_stamps.py --phases). Level
-  // 2 slows the loop; level 1 leaves it untouched. Ignored by the shipped build.
+  // 2 slows the loop; level 1 leaves it untouched. Ignored by the shipped build, and by a launch
+  // with more than stamp_rows workgroups.
   uint64_t* stamps = nullptr;
   int64_t stamp_rows = 0;
 };
 int pick_fn(int N, int epi, int half);
-// diagnostic: later launches with at most `blocks` workgroups write 8 stamps per workgroup into buf,
-// and the per-phase rows too if it has 5 rows for each (builds with -DCS336_G8_STAMP; returns false
-// in other builds). blocks 0 = off.
-bool set_stamp_buffer(uint64_t* buf, int64_t blocks);
+// whether this build writes stamps at all (built with -DCS336_G8_STAMP)
+bool stamps_built();
+// gemm8 and gemm8w address each operand (gemm8: and each tile's output rows) through one buffer
+// descriptor with 32-bit byte offsets: every such extent in bytes must be < kDmaLimit. The extents
+// are even (2-byte elements), so this is the same set that the two former spellings accepted:
+// `< 2^31 - 2^20` here and `not >= 0x7fffffff - 2^20`, which differ at the odd 2^31 - 2^20 - 1 only.
+constexpr int64_t kDmaLimit = (int64_t(1) << 31) - (int64_t(1) << 20);
 bool launch(const Args& p, int epi, int fn, hipStream_t s);
 
 // Weight gradient with both operands MN-major (csrc/gemm/gemm8w.hip): C[m][n] = Σ_t A[t][m]·B[t][n],
@@ -63,8 +67,8 @@ struct WArgs {
   int M, N, K;
   int splits;
   int trans_out, accumulate;
-  // diagnostic builds only (-DCS336_G8_STAMP, scripts/gemm8w_stamps.py): the buffer of
-  // set_stamp_buffer, 4 rows of 8 uint64 per workgroup (split-major) -- per wave group the cycles of
+  // diagnostic builds only (-DCS336_G8_STAMP, scripts/gemm8w_stamps.py): the same buffer as
+  // Args::stamps, 4 rows of 8 uint64 per workgroup (split-major) -- per wave group the cycles of
   // each of the four phases, summed over a few k-tiles in the middle of the range: reads + DMA issue
   // + counted waits, the wait at the barrier before the MFMA cluster, from there to the next barrier;
   // then the number of stamped k-tiles, the k-tiles, HW_ID, XCC_ID. Ignored by the shipped build,

@@ -62,41 +62,27 @@
 // * XCD-aware bijective block remap + grouped tile order (8 tile-rows) for L2 reuse.
 #include "cs336/kernels.h"
 #include "gemm8.h"
+#include "gemm_common.h"
 
 namespace cs336 {
 namespace gemm8 {
 
-
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+using namespace gemm_common;
+
 typedef __attribute__((ext_vector_type(4))) unsigned int v4u32;
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-constexpr int BM = 256, BK = 64, NT = 512;
-constexpr int kGroupM = 8;
-
-__device__ __forceinline__ int xcd_remap(int bid, int total) {
-  const int xcd = bid & 7, q = total >> 3, r = total & 7;
-  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + (bid >> 3);
-}
-
-__device__ __forceinline__ void sbarrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-template <int N>
-__device__ __forceinline__ void vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // sigmoid with the hardware reciprocal (v_exp_f32 + v_rcp_f32): the epilogues run outside the MFMA
 // stream, so every VALU instruction there is on the tile's critical path
 __device__ __forceinline__ float sigmoid_f(float a) { return __builtin_amdgcn_rcpf(1.f + __expf(-a)); }
+
+// four fp32 accumulators as four bf16 (round to nearest even), 8 B
+__device__ __forceinline__ uint2 pack4(f32x4 v) {
+  const uint32_t lo = (uint32_t)f32_to_bf16(v[0]) | ((uint32_t)f32_to_bf16(v[1]) << 16);
+  const uint32_t hi = (uint32_t)f32_to_bf16(v[2]) | ((uint32_t)f32_to_bf16(v[3]) << 16);
+  return make_uint2(lo, hi);
+}
 
 // Geometry of one instantiation.
 template <int FN>
@@ -144,14 +130,10 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(const Args p) {
   // N % 8 == 0: the vocabulary head, 10000 = 31·320 + 80): B rows >= N read zeros, stores masked
   const int tiles_n = NTAIL ? (p.N + BN - 1) / BN : p.N / BN;
   const int tiles_m = p.M / BM;
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int per_group = kGroupM * tiles_n;
-  const int first_m = (bid / per_group) * kGroupM;
-  const int gsz = min(tiles_m - first_m, kGroupM);
-  const int tm = first_m + (bid % per_group) % gsz, tn = (bid % per_group) / gsz;
-  const int m0 = tm * BM;
+  const Tile tile = tile_of_block(blockIdx.x, gridDim.x, tiles_m, tiles_n);
+  const int m0 = tile.tm * BM;
   // EPI 1: tile column c < BN/2 is W1 row j0 + c, else W3 row half + j0 + c - BN/2
-  const int n0 = tn * (EPI == 1 ? BN / 2 : BN);
+  const int n0 = tile.tn * (EPI == 1 ? BN / 2 : BN);
 
   // ---- DMA setup: per wave G_ALL granules; slot order P1 (A0 then B0), P2 (B1), P3 (A1) ------
   // The record counts end at each operand's last element (host: both extents < 2 GiB), so B rows
@@ -300,32 +282,9 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(const Args p) {
     __builtin_amdgcn_s_setprio(0);
   };
 
-#if CS336_G8_STAMP >= 2
-  // -DCS336_G8_STAMP=2, stamp buffer with room for the per-phase rows (5 rows per workgroup): kStampTiles
-  // k-tiles in the middle of the range are stamped at every phase's entry (3p), after its reads / DMA
-  // issue / waits (3p + 1) and after the barrier before its MFMA cluster (3p + 2); 3 kPhases = after
-  // the last barrier. Sums of the three segments per phase and wave group leave through the stamp
-  // buffer (scripts/gemm8_stamps.py --phases; the rows have room for four phases)
-  constexpr int kStampTiles = 4, kPhases = 2;
-  const bool st_ph = p.stamps && p.stamp_rows >= 5 * (int64_t)gridDim.x;
-  const int s_lo = nkt > kStampTiles ? (nkt - kStampTiles) / 2 : 0;
-  uint32_t s_work[4] = {0, 0, 0, 0}, s_wait[4] = {0, 0, 0, 0}, s_mma[4] = {0, 0, 0, 0}, s_cnt = 0;
-  auto stamp = [&]() -> uint32_t {
-    uint64_t v;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return (uint32_t)v;
-  };
-#define CS336_G8_PSTAMP(I) \
-  do {                     \
-    if (samp) ts_[I] = stamp(); \
-  } while (0)
-#else
-#define CS336_G8_PSTAMP(I) \
-  do {                     \
-  } while (0)
-#endif
+  // -DCS336_G8_STAMP=2 and a stamp buffer with room for the per-phase rows (5 rows per workgroup):
+  // per-phase stamps of a few k-tiles (PhaseStamps, gemm_common.h; scripts/gemm8_stamps.py --phases)
+  PhaseStamps<(kStampLevel >= 2)> ps(p.stamps && p.stamp_rows >= 5 * (int64_t)gridDim.x, nkt);
 
   // ---- prologue: k-tiles 0 and 1 -------------------------------------------------------------
   issue(0, 0, 0);
@@ -343,14 +302,10 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(const Args p) {
 
   for (int t = 0; t < nkt; ++t) {
     const bool more1 = t + 1 < nkt, more2 = t + 2 < nkt;  // k-tile t+1 / t+2 exists
-#if CS336_G8_STAMP >= 2
-    const bool samp = st_ph && t >= s_lo && t < s_lo + kStampTiles;
-    uint32_t ts_[3 * kPhases + 1] = {};
-#endif
     // Phase A: rows 0-63 x all column tiles. Restage the other stage's Y region (last read in phase
     // B of k-tile t-1) with k-tile t+1 -- k-tile 1 came whole from the prologue; retire Y(t), which
     // phase B reads
-    CS336_G8_PSTAMP(0);
+    ps.begin(t);  // mark 0
     if (t > 0 && more1) issue(2, t + 1, (t + 1) & 1);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -363,12 +318,12 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(const Args p) {
     if (more1) vmcnt<G::G_ALL>();  // younger: X(t+1), Y(t+1)
     else vmcnt<0>();
     lgkm0();
-    CS336_G8_PSTAMP(1);
+    ps.mark(1);
     sbarrier();
-    CS336_G8_PSTAMP(2);
+    ps.mark(2);
     mma(0);
     sbarrier();
-    CS336_G8_PSTAMP(3);
+    ps.mark(3);
     // Phase B: rows 64-127 x all column tiles (B fragments kept). Restage this stage's X region (its
     // reads retired in phase A) with k-tile t+2; retire X(t+1), which phase A of k-tile t+1 reads
     if (more2) issue(1, t + 2, t & 1);
@@ -379,49 +334,23 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(const Args p) {
     if (more2) vmcnt<G::G_ALL>();      // younger: Y(t+1), X(t+2)
     else if (more1) vmcnt<G::G_Y>();   // younger: Y(t+1)
     lgkm0();
-    CS336_G8_PSTAMP(4);
+    ps.mark(4);
     sbarrier();
-    CS336_G8_PSTAMP(5);
+    ps.mark(5);
     mma(4);
     next_stage(t);
     sbarrier();
-    CS336_G8_PSTAMP(6);
-#if CS336_G8_STAMP >= 2
-    if (samp) {
-#pragma unroll
-      for (int ph = 0; ph < kPhases; ++ph) {
-        s_work[ph] += ts_[3 * ph + 1] - ts_[3 * ph];
-        s_wait[ph] += ts_[3 * ph + 2] - ts_[3 * ph + 1];
-        s_mma[ph] += ts_[3 * ph + 3] - ts_[3 * ph + 2];
-      }
-      ++s_cnt;
-    }
-#endif
+    ps.mark(6);
+    ps.end_tile();
   }
-#undef CS336_G8_PSTAMP
   if (wr == 0) sbarrier();  // balance the wave-group offset
   lgkm0();
   sbarrier();
 #ifdef CS336_G8_STAMP
   st_t2 = __builtin_amdgcn_s_memtime();
 #endif
-#if CS336_G8_STAMP >= 2
-  // per-phase rows behind the workgroups' own rows, 4 rows of 8 per workgroup: wave group g -> rows
-  // 2g (work[4], wait[4]) and 2g + 1 (mma[4], stamped k-tiles, k-tiles, HW_ID, XCC_ID)
-  if (st_ph && lane == 0 && wc == 0) {
-    uint32_t hw, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    uint64_t* o = p.stamps + 8 * (int64_t)gridDim.x + 32 * (int64_t)blockIdx.x + 16 * wr;
-#pragma unroll
-    for (int ph = 0; ph < kPhases; ++ph) {
-      o[ph] = s_work[ph];
-      o[4 + ph] = s_wait[ph];
-      o[8 + ph] = s_mma[ph];
-    }
-    o[12] = s_cnt; o[13] = (uint64_t)nkt; o[14] = hw; o[15] = xcc;
-  }
-#endif
+  // per-phase rows behind the workgroups' own rows, 4 rows of 8 per workgroup, two per wave group
+  if (ps.kOn && lane == 0 && wc == 0) ps.store(p.stamps + 8 * (int64_t)gridDim.x + 32 * (int64_t)blockIdx.x + 16 * wr, nkt);
 
   // ---- epilogue ----------------------------------------------------------------------------
   // cache policy of the epilogue's streams: the SwiGLU outputs (EPI 1 y and h, EPI 2 da|db) and the
@@ -453,9 +382,7 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(const Args p) {
       for (int j = 0; j < FN; ++j) {
         const f32x4 v = acc[i][j];
         const int row = arow + 16 * i + m_l, col = bcol + 16 * j + n_l;
-        const uint32_t lo = (uint32_t)f32_to_bf16(v[0]) | ((uint32_t)f32_to_bf16(v[1]) << 16);
-        const uint32_t hi = (uint32_t)f32_to_bf16(v[2]) | ((uint32_t)f32_to_bf16(v[3]) << 16);
-        *reinterpret_cast<uint2*>(smem + img(row, col >> 3) + ((col >> 2) & 1) * 8) = make_uint2(lo, hi);
+        *reinterpret_cast<uint2*>(smem + img(row, col >> 3) + ((col >> 2) & 1) * 8) = pack4(v);
       }
     // output (and EPI 2 input) descriptors based at the tile's first row; 32-bit offsets within it
     const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(
@@ -583,9 +510,7 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(const Args p) {
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
           const f32x4 v = acc[piece * (PR / 16) + ib][j];
-          const uint32_t lo = (uint32_t)f32_to_bf16(v[0]) | ((uint32_t)f32_to_bf16(v[1]) << 16);
-          const uint32_t hi = (uint32_t)f32_to_bf16(v[2]) | ((uint32_t)f32_to_bf16(v[3]) << 16);
-          *reinterpret_cast<uint2*>(scr + ((16 * ib + m_l) * WTN + 16 * j + n_l) * 2) = make_uint2(lo, hi);
+          *reinterpret_cast<uint2*>(scr + ((16 * ib + m_l) * WTN + 16 * j + n_l) * 2) = pack4(v);
         }
       __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -622,17 +547,13 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(const Args p) {
   __syncthreads();
   if (tid == 0 && p.stamps) {
     uint32_t hw, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    hw_ids(hw, xcc);
     uint64_t* o = p.stamps + 8 * (int64_t)blockIdx.x;
     const uint64_t t3 = __builtin_amdgcn_s_memtime(), r3 = __builtin_amdgcn_s_memrealtime();
     o[0] = st_t0; o[1] = st_t1; o[2] = st_t2; o[3] = t3; o[4] = st_r0; o[5] = r3; o[6] = hw; o[7] = xcc;
   }
 #endif
 }
-
-uint64_t* g_stamps = nullptr;  // diagnostic stamp buffer (set_stamp_buffer), null in normal runs
-int64_t g_stamp_blocks = 0;
 
 template <int FN, int EPI>
 void launch_t(const Args& p_in, hipStream_t s) {
@@ -641,10 +562,7 @@ void launch_t(const Args& p_in, hipStream_t s) {
   const int tail = EPI == 0 ? (p.N % BN != 0 ? 1 : 0) | (p.K % BK != 0 ? 2 : 0) : 0;
   const int tiles_n = (tail & 1) ? (p.N + BN - 1) / BN : p.N / BN;
   const dim3 grid((unsigned)((p.M / BM) * tiles_n)), block(NT);
-  if (g_stamps && (int64_t)grid.x <= g_stamp_blocks) {
-    p.stamps = g_stamps;
-    p.stamp_rows = g_stamp_blocks;
-  }
+  if ((int64_t)grid.x > p.stamp_rows) p.stamps = nullptr;
   if constexpr (EPI == 0) {
     if (tail == 1) {
       hipLaunchKernelGGL((gemm8_kernel<FN, 0, 1>), grid, block, 0, s, p);
@@ -664,15 +582,7 @@ void launch_t(const Args& p_in, hipStream_t s) {
 
 }  // namespace
 
-bool set_stamp_buffer(uint64_t* buf, int64_t blocks) {
-  g_stamps = blocks > 0 ? buf : nullptr;
-  g_stamp_blocks = blocks > 0 ? blocks : 0;
-#ifdef CS336_G8_STAMP
-  return true;
-#else
-  return false;  // this build writes no stamps
-#endif
-}
+bool stamps_built() { return kStampLevel > 0; }
 
 // Tile width for an output of N columns (EPI 1: N = 2·half): 320 if it divides, else 256, else 0.
 int pick_fn(int N, int epi, int half) {
@@ -698,16 +608,15 @@ bool launch(const Args& p, int epi, int fn, hipStream_t s) {
   if (fn != 4 && fn != 5) return false;
   if (epi != 0 && p.N % (64 * fn)) return false;
   // one DMA descriptor per operand with 32-bit offsets: both extents below 2 GiB
-  const int64_t lim = (int64_t)0x7fffffff - (1 << 20);
-  if (((int64_t)(BM - 1) * p.lda + p.K) * 2 >= lim || ((int64_t)(p.N - 1) * p.ldb + p.K) * 2 >= lim) return false;
+  if (((int64_t)(BM - 1) * p.lda + p.K) * 2 >= kDmaLimit || ((int64_t)(p.N - 1) * p.ldb + p.K) * 2 >= kDmaLimit) return false;
   // the EPI 0-2 epilogue streams (C, h, y) go through per-tile buffer descriptors with 32-bit byte
   // offsets from the tile's first row: one tile's row range must stay below 2 GiB (EPI 3 stores
   // through 64-bit pointers)
   if (epi != 3) {
     const int64_t c_cols = epi == 2 ? (int64_t)p.N + p.half : (int64_t)p.N;  // EPI 2: [da|db]
-    if (((int64_t)(BM - 1) * p.ldc + c_cols) * 2 >= lim) return false;
-    if (epi == 1 && ((int64_t)(BM - 1) * p.ldh + p.half) * 2 >= lim) return false;
-    if (epi == 2 && ((int64_t)(BM - 1) * p.ldy + p.N + p.half) * 2 >= lim) return false;
+    if (((int64_t)(BM - 1) * p.ldc + c_cols) * 2 >= kDmaLimit) return false;
+    if (epi == 1 && ((int64_t)(BM - 1) * p.ldh + p.half) * 2 >= kDmaLimit) return false;
+    if (epi == 2 && ((int64_t)(BM - 1) * p.ldy + p.N + p.half) * 2 >= kDmaLimit) return false;
   }
 #define CS336_G8(F, E)        \
   do {                        \

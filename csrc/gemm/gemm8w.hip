@@ -46,36 +46,16 @@
 //   split-K slab; rows beyond M (the last, padded row tile) are computed and dropped.
 #include "cs336/kernels.h"
 #include "gemm8.h"
+#include "gemm_common.h"
 
 namespace cs336 {
 namespace gemm8 {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+using namespace gemm_common;
+
 typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-constexpr int BM = 256, BK = 64, NT = 512;
-constexpr int kGroupM = 8;
-
-__device__ __forceinline__ int xcd_remap(int bid, int total) {
-  const int xcd = bid & 7, q = total >> 3, r = total & 7;
-  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + (bid >> 3);
-}
-__device__ __forceinline__ void sbarrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-template <int N>
-__device__ __forceinline__ void vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // 32-B slot swizzle of an MN-major image row t (S = row bytes): the 8 rows {0..3, 8..11} (+4) a
 // 32-lane half of a transposed fragment read touches map to 8 distinct slots of a 256-B bank row
@@ -84,6 +64,16 @@ __device__ __forceinline__ int swz(int t) {
   static_assert(S % 256 == 0 || S % 256 == 128, "row bytes");
   if constexpr (S % 256 == 0) return (t & 3) | (((t >> 3) & 1) << 2);
   else return ((t >> 1) & 1) | (((t >> 3) & 1) << 1);  // rows alternate 128-B bank halves already
+}
+
+// one lane's 16 B of the result: stored, or added to what is there
+__device__ __forceinline__ void store4(float4* d, f32x4 v, int accumulate) {
+  float4 w = make_float4(v[0], v[1], v[2], v[3]);
+  if (accumulate) {
+    const float4 o = *d;
+    w.x += o.x; w.y += o.y; w.z += o.z; w.w += o.w;
+  }
+  *d = w;
 }
 
 template <int FN>
@@ -107,12 +97,8 @@ __global__ __launch_bounds__(NT, 2) void gemm8w_kernel(const WArgs p) {
   const int wr = wave >> 2, wc = wave & 3;
 
   const int tiles_n = p.N / BN, tiles_m = (p.M + BM - 1) / BM;
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int per_group = kGroupM * tiles_n;
-  const int first_m = (bid / per_group) * kGroupM;
-  const int gsz = min(tiles_m - first_m, kGroupM);
-  const int tm = first_m + (bid % per_group) % gsz, tn = (bid % per_group) / gsz;
-  const int m0 = tm * BM, n0 = tn * BN;
+  const Tile tile = tile_of_block(blockIdx.x, gridDim.x, tiles_m, tiles_n);
+  const int m0 = tile.tm * BM, n0 = tile.tn * BN;
 
   const int nkt_all = p.K / BK, split = blockIdx.y, nsplit = gridDim.y;
   const int kt0 = (int)((int64_t)nkt_all * split / nsplit), kt1 = (int)((int64_t)nkt_all * (split + 1) / nsplit);
@@ -263,31 +249,9 @@ __global__ __launch_bounds__(NT, 2) void gemm8w_kernel(const WArgs p) {
     }
   };
 
-#ifdef CS336_G8_STAMP
-  // diagnostic build: kStampTiles k-tiles in the middle of this workgroup's range are stamped at
-  // every phase's entry (3p), after its reads / DMA issue / waits (3p + 1) and after the barrier
-  // before its MFMA cluster (3p + 2); 3 kPhases = after the last barrier. Sums of the three segments
-  // per phase leave through the stamp buffer only (scripts/gemm8w_stamps.py; its rows have room for
-  // four phases)
-  constexpr int kStampTiles = 4, kPhases = 2;
-  const int s_lo = nkt > kStampTiles ? (nkt - kStampTiles) / 2 : 0;
-  uint32_t s_work[4] = {0, 0, 0, 0}, s_wait[4] = {0, 0, 0, 0}, s_mma[4] = {0, 0, 0, 0}, s_cnt = 0;
-  auto stamp = [&]() -> uint32_t {
-    uint64_t v;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return (uint32_t)v;
-  };
-#define CS336_G8W_STAMP(I) \
-  do {                     \
-    if (samp) ts_[I] = stamp(); \
-  } while (0)
-#else
-#define CS336_G8W_STAMP(I) \
-  do {                     \
-  } while (0)
-#endif
+  // diagnostic builds (-DCS336_G8_STAMP, any level): per-phase stamps of a few k-tiles in the middle
+  // of this workgroup's range (PhaseStamps, gemm_common.h; scripts/gemm8w_stamps.py)
+  PhaseStamps<(kStampLevel >= 1)> ps(true, nkt);
 
   // the two counted waits of a K-tile (constants: header comment)
   auto wait_h1 = [&](bool more1) {  // retires this K-tile's second half
@@ -319,71 +283,42 @@ __global__ __launch_bounds__(NT, 2) void gemm8w_kernel(const WArgs p) {
 
   for (int t = 0; t < nkt; ++t) {
     const bool more1 = t + 1 < nkt, more2 = t + 2 < nkt;
-#ifdef CS336_G8_STAMP
-    const bool samp = t >= s_lo && t < s_lo + kStampTiles;
-    uint32_t ts_[3 * kPhases + 1] = {};
-#endif
     // P0: k 0-31, all 128 rows; restage the other stage's second half with K-tile t+1; retire this
     // K-tile's second half (read in P1)
-    CS336_G8W_STAMP(0);
+    ps.begin(t);  // mark 0
     if (more1) CS336_G8W_ISSUE(1, t + 1, (t + 1) & 1);
     read_x(0);
     read_y(0);
     read_b(0);
     wait_h1(more1);
     lgkm0();
-    CS336_G8W_STAMP(1);
+    ps.mark(1);
     sbarrier();
-    CS336_G8W_STAMP(2);
+    ps.mark(2);
     mma();
     sbarrier();
     // P1: k 32-63; restage this stage's first half with K-tile t+2; retire K-tile t+1's first half
-    CS336_G8W_STAMP(3);
+    ps.mark(3);
     if (more2) CS336_G8W_ISSUE(0, t + 2, t & 1);
     read_x(1);
     read_y(1);
     read_b(1);
     wait_h0(more1, more2);
     lgkm0();
-    CS336_G8W_STAMP(4);
+    ps.mark(4);
     sbarrier();
-    CS336_G8W_STAMP(5);
+    ps.mark(5);
     mma();
     next_stage(t);
     sbarrier();
-    CS336_G8W_STAMP(6);
-#ifdef CS336_G8_STAMP
-    if (samp) {
-#pragma unroll
-      for (int ph = 0; ph < kPhases; ++ph) {
-        s_work[ph] += ts_[3 * ph + 1] - ts_[3 * ph];
-        s_wait[ph] += ts_[3 * ph + 2] - ts_[3 * ph + 1];
-        s_mma[ph] += ts_[3 * ph + 3] - ts_[3 * ph + 2];
-      }
-      ++s_cnt;
-    }
-#endif
+    ps.mark(6);
+    ps.end_tile();
   }
 #undef CS336_G8W_ISSUE
-#undef CS336_G8W_STAMP
   if (wr == 0) sbarrier();
-#ifdef CS336_G8_STAMP
-  // 4 rows of 8 per workgroup: wave group g -> rows 2g (work[4], wait[4]) and 2g + 1 (mma[4],
-  // stamped k-tiles, k-tiles, HW_ID, XCC_ID)
-  if (p.stamps && lane == 0 && wc == 0) {
-    uint32_t hw, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    uint64_t* o = p.stamps + 32 * ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) + 16 * wr;
-#pragma unroll
-    for (int ph = 0; ph < kPhases; ++ph) {
-      o[ph] = s_work[ph];
-      o[4 + ph] = s_wait[ph];
-      o[8 + ph] = s_mma[ph];
-    }
-    o[12] = s_cnt; o[13] = (uint64_t)nkt; o[14] = hw; o[15] = xcc;
-  }
-#endif
+  // 4 rows of 8 per workgroup (split-major), two per wave group
+  if (ps.kOn && p.stamps && lane == 0 && wc == 0)
+    ps.store(p.stamps + 32 * ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) + 16 * wr, nkt);
 
   // ---- epilogue: fp32 straight from the accumulators, 16 B per lane ----------------------------
   float* c = p.c + (int64_t)split * p.slab_stride;
@@ -396,26 +331,10 @@ __global__ __launch_bounds__(NT, 2) void gemm8w_kernel(const WArgs p) {
       if constexpr (TRANS) {
         // C[m .. m+3][n] -> Cᵀ row n, columns m .. m+3
         const int m = m0 + arow + 16 * i + lq, n = n0 + bcol + 16 * j + lr;
-        if (m < p.M) {
-          float4* d = reinterpret_cast<float4*>(c + (int64_t)n * p.ldc + m);
-          float4 w = make_float4(v[0], v[1], v[2], v[3]);
-          if (p.accumulate) {
-            const float4 o = *d;
-            w.x += o.x; w.y += o.y; w.z += o.z; w.w += o.w;
-          }
-          *d = w;
-        }
+        if (m < p.M) store4(reinterpret_cast<float4*>(c + (int64_t)n * p.ldc + m), v, p.accumulate);
       } else {
         const int m = m0 + arow + 16 * i + lr, n = n0 + bcol + 16 * j + lq;
-        if (m < p.M) {
-          float4* d = reinterpret_cast<float4*>(c + (int64_t)m * p.ldc + n);
-          float4 w = make_float4(v[0], v[1], v[2], v[3]);
-          if (p.accumulate) {
-            const float4 o = *d;
-            w.x += o.x; w.y += o.y; w.z += o.z; w.w += o.w;
-          }
-          *d = w;
-        }
+        if (m < p.M) store4(reinterpret_cast<float4*>(c + (int64_t)m * p.ldc + n), v, p.accumulate);
       }
     }
 }

@@ -5,6 +5,8 @@
 //
 //  * tile_order / xcd_remap (fa_common.h): every causal / non-causal FA2 grid maps block ids to
 //    (batch*head, tile level) BIJECTIVELY, for every head-group size the host can pick;
+//  * tile_of_block (gemm/gemm_common.h): the grouped tile order of the three MFMA GEMM kernels maps
+//    the block ids of a grid of tiles_m x tiles_n workgroups onto its tiles BIJECTIVELY;
 //  * swz / lds_off: the XOR-swizzled LDS images keep every 16-B chunk of a row inside the row and
 //    the row-fragment (ds_read_b128) and transposed (ds_read_b64_tr_b16) reads bank-conflict free
 //    for every row width the kernels instantiate (64, 128, 192, 256 B; 128 is also the dSᵀ image),
@@ -16,6 +18,7 @@
 #include <set>
 #include <vector>
 
+#include "../gemm/gemm_common.h"
 #include "cs336/tensile_names.h"
 #include "fa_bwd_common.h"
 
@@ -60,6 +63,31 @@ static void check_tile_order() {
     CHECK((int)ids.size() == total && *ids.begin() == 0 && *ids.rbegin() == total - 1, "xcd_remap not a permutation of %d", total);
   }
   std::printf("tile_order: %ld block ids checked\n", checked);
+}
+
+// tiles_m 204 is the XL token count in 256-row tiles (52,224 / 256); tiles_n 1..40 covers every
+// column-tile count of the model's projections and the odd ones that leave a partial last group
+static void check_gemm_tile_order() {
+  std::vector<int> tms;
+  for (int m = 1; m <= 20; ++m) tms.push_back(m);
+  for (int m : {33, 192, 204}) tms.push_back(m);
+  long checked = 0;
+  for (int tiles_m : tms)
+    for (int tiles_n : {1, 2, 3, 5, 8, 15, 32, 40}) {
+      const int blocks = tiles_m * tiles_n;
+      std::vector<char> seen((size_t)blocks, 0);
+      for (int b = 0; b < blocks; ++b) {
+        const gemm_common::Tile t = gemm_common::tile_of_block(b, blocks, tiles_m, tiles_n);
+        const bool in = t.tm >= 0 && t.tm < tiles_m && t.tn >= 0 && t.tn < tiles_n;
+        CHECK(in, "tile_of_block out of range tiles_m=%d tiles_n=%d block=%d -> (%d,%d)", tiles_m, tiles_n, b, t.tm, t.tn);
+        if (!in) continue;
+        char& s = seen[(size_t)t.tm * tiles_n + t.tn];
+        CHECK(!s, "tile_of_block not injective tiles_m=%d tiles_n=%d (%d,%d)", tiles_m, tiles_n, t.tm, t.tn);
+        s = 1;
+        ++checked;
+      }
+    }
+  std::printf("gemm tile order: %ld block ids checked\n", checked);
 }
 
 template <int RB>
@@ -154,6 +182,7 @@ static void check_row_perm() {
 int main() {
   check_row_perm();
   check_tile_order();
+  check_gemm_tile_order();
   check_swizzle<64>();
   check_swizzle<128>();
   check_swizzle<192>();
