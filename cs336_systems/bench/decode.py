@@ -10,16 +10,22 @@ cache sliced to kv_len), the only way to compute a decode step without the kerne
 Skinny-M GEMM table (``--skinny``): ``cs336::gemm_skinny`` (``csrc/gemm/gemm_skinny.hip``) on the five
 projection shapes (qkv, o, w1|w3, w2, lm_head at the GPT-2 vocabulary 50257) of ``xl`` and ``2.7b`` at
 M 1 / 8 / 16, bf16, under the same ``do_bench`` protocol: us and GB/s of W bytes against the achievable
-HBM rate, with ``torch.mm`` on the same operands alongside.
+HBM rate, with ``torch.mm`` on the same operands alongside. ``--fp8`` adds, per row, the FP8 weight-only
+kernel ``cs336::gemm_skinny_w8`` (``csrc/gemm/gemm_skinny_w8.hip``) on ``quantize_fp8_rows(w)``: median and
+q20-q80 over the same 50 flushed calls, GB/s of FP8 bytes, and the ratio to the bf16 skinny kernel of
+the same run.
 
 End to end: tokens/s of ``generate`` with ``use_cache=True`` against ``use_cache=False`` (a full
 forward over the window per token) and against ``use_cache=True, graph=True`` (the cached step
 replayed from a HIP graph over the skinny-M kernel), model ``xl`` held in bf16. ``--arms`` picks the
-arms (the uncached one takes minutes at context 4096).
+arms (the uncached one takes minutes at context 4096); ``graph+fp8`` is the graph arm over
+``Fp8DecodeWeights`` (``generate(..., graph=True, weights=qw)``). The graph arms also report the replayed
+step alone (HIP events around 50 replays on a cache holding the prompt, truncated back every time).
 
     python -m cs336_systems.bench.decode --json profiles/decode_attention.json
     python -m cs336_systems.bench.decode --no-e2e --batch 8 --kv-len 4096
     python -m cs336_systems.bench.decode --no-kernel --skinny --arms cached graph --json profiles/decode_graph.json
+    python -m cs336_systems.bench.decode --no-kernel --skinny --fp8 --arms graph graph+fp8 --json profiles/decode_fp8.json
 
 Chunk tables (``--chunk``): ``ops.decode_attention_chunk`` (``csrc/flash_attn/fa_decode_chunk.hip``) at
 n in {1, 2, 4, 8, 16} query rows over the same (B, H, d, kv_len) points: us, GB/s of K+V bytes (read
@@ -168,7 +174,8 @@ def skinny_shapes(model_size: str) -> list[tuple[str, int, int]]:
     return [("qkv", 3 * d, d), ("o", d, d), ("w1|w3", 2 * f, d), ("w2", d, f), ("lm_head", LM_HEAD_VOCAB, d)]
 
 
-def skinny_row(model_size: str, name: str, M: int, N: int, K: int, warmup: int = 10, rep: int = 50) -> dict:
+def skinny_row(model_size: str, name: str, M: int, N: int, K: int, warmup: int = 10, rep: int = 50,
+               fp8: bool = False) -> dict:
     from ..ops import gemm
 
     dev, dt = "cuda", torch.bfloat16
@@ -191,12 +198,53 @@ def skinny_row(model_size: str, name: str, M: int, N: int, K: int, warmup: int =
     row["speedup_vs_mm"] = row["mm_us"] / row["skinny_us"]
     torch.ops.cs336.gemm_skinny(x, w, out)
     row["max_abs_diff_vs_mm"] = (out.float() - torch.mm(x, w.t()).float()).abs().max().item()
+    if fp8:
+        wq, scale = ops.quantize_fp8_rows(w)
+        assert gemm.skinny_w8_ok(x, wq, scale)
+        q_bytes = float(N * K * wq.element_size() + N * scale.element_size())
+        row["fp8_us"], row["fp8_us_q20"], row["fp8_us_q80"] = t(lambda: torch.ops.cs336.gemm_skinny_w8(x, wq, scale, out))
+        row["fp8_mbytes"] = q_bytes / 2**20
+        row["fp8_gbs"] = q_bytes / (row["fp8_us"] * 1e-6) / 1e9
+        row["fp8_hbm_frac"] = row["fp8_gbs"] / HBM_ACHIEVABLE_GBS
+        row["fp8_vs_skinny"] = row["fp8_us"] / row["skinny_us"]  # below 1: the FP8 kernel is faster
+        # faster / slower only beyond the q20-q80 spread of both sides
+        row["fp8_verdict"] = ("faster" if row["fp8_us_q80"] < row["skinny_us_q20"] else
+                              "slower" if row["fp8_us_q20"] > row["skinny_us_q80"] else "same")
+        ref = ops.skinny_linear_fp8_ref(x, wq, scale)
+        row["fp8_max_abs_diff_vs_ref"] = (out.float() - ref.float()).abs().max().item()
+        del wq, scale
     del x, w, out
     torch.cuda.empty_cache()
     return row
 
 
-ARMS = {"cached": dict(use_cache=True), "uncached": dict(use_cache=False), "graph": dict(use_cache=True, graph=True)}
+ARMS = {"cached": dict(use_cache=True), "uncached": dict(use_cache=False), "graph": dict(use_cache=True, graph=True),
+        "graph+fp8": dict(use_cache=True, graph=True)}  # (+ weights=Fp8DecodeWeights(model), built per model)
+ARM_KEYS = {"graph": "cached_graph", "graph+fp8": "cached_graph_fp8"}
+
+
+def replay_ms(model, x: torch.Tensor, weights=None, rep: int = 50) -> tuple[float, float, float]:
+    """Median, q20 and q80 ms of one replayed decode step on a cache holding the prompt ``x`` (HIP
+    events around the replay; the cache is truncated back after every step)."""
+    from ..models import DecodeGraph
+    from ..models.kv_cache import KVCache
+
+    B, prompt = x.shape
+    cache = KVCache(model, B)
+    model.forward_cached(x, cache)
+    dg = DecodeGraph(model, cache, capture=True, weights=weights)
+    tok, ts = x[:, -1:], []
+    for r in range(rep + 5):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        dg.step(tok)
+        b.record()
+        b.synchronize()
+        cache.truncate(prompt)
+        if r >= 5:  # the first rounds warm clocks and caches
+            ts.append(a.elapsed_time(b))
+    ts.sort()
+    return ts[len(ts) // 2], ts[len(ts) // 5], ts[len(ts) * 4 // 5]
 
 
 def e2e_row(model_size: str, ctx: int, B: int, prompt: int, new: int, arms=("cached", "uncached", "graph")) -> dict:
@@ -206,8 +254,15 @@ def e2e_row(model_size: str, ctx: int, B: int, prompt: int, new: int, arms=("cac
     model = build_model(model_size, ctx, device="cuda").to(torch.bfloat16).eval()
     x = torch.randint(0, model.vocab_size, (B, prompt), device="cuda")
     row = dict(model=model_size, context_length=ctx, B=B, prompt=prompt, new_tokens=new, dtype="bf16")
+    qw = None
     for arm in arms:
-        kw = ARMS[arm]
+        kw = dict(ARMS[arm])
+        if arm == "graph+fp8":
+            from ..models import Fp8DecodeWeights
+
+            qw = qw or Fp8DecodeWeights(model)
+            kw["weights"] = qw
+            row["fp8_weight_mbytes"] = qw.nbytes / 2**20
         model.generate(x, 4, top_k=1, **kw)  # warm-up: GEMM selection, allocator
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -215,14 +270,20 @@ def e2e_row(model_size: str, ctx: int, B: int, prompt: int, new: int, arms=("cac
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         assert out.shape == (B, new)
-        name = "cached_graph" if arm == "graph" else arm
+        name = ARM_KEYS.get(arm, arm)
         row[f"{name}_s"] = dt
         row[f"{name}_tok_s"] = B * new / dt
         row[f"{name}_ms_per_step"] = dt / new * 1e3
+        if arm in ARM_KEYS:
+            med, lo, hi = replay_ms(model, x, kw.get("weights"))
+            row[f"{name}_replay_ms"], row[f"{name}_replay_ms_q20"], row[f"{name}_replay_ms_q80"] = med, lo, hi
     if "cached_s" in row and "uncached_s" in row:
         row["speedup"] = row["uncached_s"] / row["cached_s"]
     if "cached_s" in row and "cached_graph_s" in row:
         row["graph_speedup_vs_cached"] = row["cached_s"] / row["cached_graph_s"]
+    if "cached_graph_s" in row and "cached_graph_fp8_s" in row:
+        row["fp8_speedup_vs_graph"] = row["cached_graph_s"] / row["cached_graph_fp8_s"]
+        row["fp8_replay_vs_graph"] = row["cached_graph_fp8_replay_ms"] / row["cached_graph_replay_ms"]
     del model
     torch.cuda.empty_cache()
     return row
@@ -239,6 +300,7 @@ def main(argv=None):
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--model", default="xl")
     ap.add_argument("--skinny", action="store_true", help="the skinny-M GEMM table (xl and 2.7b projections)")
+    ap.add_argument("--fp8", action="store_true", help="with --skinny: add the FP8 weight-only kernel to every row")
     ap.add_argument("--chunk", action="store_true",
                     help="the multi-token tables: decode_attention_chunk rows instead of the single-token sweep, and "
                          "(with --arms verify) the replayed n-token step; no generate arms")
@@ -288,7 +350,7 @@ def main(argv=None):
         for size in ("xl", "2.7b"):
             for name, N, K in skinny_shapes(size):
                 for M in SKINNY_M:
-                    r = skinny_row(size, name, M, N, K, rep=a.rep)
+                    r = skinny_row(size, name, M, N, K, rep=a.rep, fp8=a.fp8)
                     out["skinny"].append(r)
                     print(json.dumps(r), flush=True)
     if not a.no_e2e:

@@ -1,6 +1,7 @@
 from .configs import DEFAULT_THETA, DEFAULT_VOCAB, MODEL_CONFIGS, get_model_config, param_count, train_flops_per_token
 from .decode_graph import DecodeGraph
 from .kv_cache import KVCache
+from .quantized import Fp8DecodeWeights
 from .speculative import speculative_generate
 from .transformer import (
     BasicsTransformerLM,
@@ -32,6 +33,7 @@ __all__ = [
     "CausalMultiHeadSelfAttention",
     "DecodeGraph",
     "Embedding",
+    "Fp8DecodeWeights",
     "KVCache",
     "Linear",
     "RMSNorm",

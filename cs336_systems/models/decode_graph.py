@@ -25,6 +25,13 @@ every weight per token -- hold the model in bf16.
 chunk. Its projections have ``B * n`` rows; up to 16 they run the skinny kernel, which reads every
 weight once whatever the row count, and above that the ordinary GEMM path. ``cache.truncate`` is, like
 ``reset``, an in-place update of ``cache.lengths`` and leaves the graph valid.
+
+``weights=qw`` (an ``Fp8DecodeWeights`` of this model, ``models/quantized.py``): the step's projections
+read the FP8 copy of their weights through ``gemm.skinny_decode(fp8=qw)`` -- the FP8 weight-streaming
+kernel (``csrc/gemm/gemm_skinny_w8.hip``) at up to 16 rows -- in the captured, the eager and the
+``tokens=n`` step alike. Only the steps a ``DecodeGraph`` runs read FP8: the prefill is an ordinary
+``forward_cached`` on the 16-bit weights. After an in-place weight update call ``qw.refresh()``, which
+requantizes in place; the next replay picks it up.
 """
 
 from __future__ import annotations
@@ -38,7 +45,7 @@ class DecodeGraph:
     """``logits = dg.step(tok)``: ``tok`` (B, tokens) int64 -> (B, tokens, vocab), the cache advanced
     by ``tokens`` (default 1)."""
 
-    def __init__(self, model, cache, capture: bool = True, warmup: int = 2, tokens: int = 1):
+    def __init__(self, model, cache, capture: bool = True, warmup: int = 2, tokens: int = 1, weights=None):
         if getattr(model, "tensor_parallel", None) is not None or any(
                 layer.attn.context_parallel is not None for layer in model.layers):
             raise NotImplementedError("DecodeGraph does not support tensor / context parallelism")
@@ -48,7 +55,9 @@ class DecodeGraph:
             raise ValueError("DecodeGraph(capture=True) captures HIP graphs: the model and cache must be on a GPU")
         if int(tokens) != tokens or tokens < 1:
             raise ValueError("DecodeGraph needs tokens >= 1")
-        self.model, self.cache, self.tokens = model, cache, int(tokens)
+        if weights is not None and getattr(weights, "model", None) is not model:
+            raise ValueError("weights= was built for a different model")
+        self.model, self.cache, self.tokens, self.weights = model, cache, int(tokens), weights
         self.graph = None
         if not capture:
             return
@@ -79,7 +88,7 @@ class DecodeGraph:
         """The step both modes run: the decode (or, for ``tokens > 1``, chunk) branch of
         ``forward_cached`` (also on an empty cache, where the warm-up's rows land at index 0, unread)
         with the fixed attention bound."""
-        with gemm.skinny_decode():
+        with gemm.skinny_decode(fp8=self.weights):
             return self.model._forward_cached(tok, self.cache, max(self.cache.length, 1), self.cache.max_len)
 
     def step(self, tok: torch.Tensor) -> torch.Tensor:

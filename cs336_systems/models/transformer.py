@@ -77,6 +77,9 @@ class Linear(nn.Module):
             return y.view(*x.shape[:-1], y.shape[-1])
         if x.is_cuda:
             return fused.fused_linear(x, self.weight)
+        hit = _gemm.fp8_lookup(self.weight)  # inside gemm.skinny_decode(fp8=...): the quantized copy
+        if hit is not None:
+            return ops.skinny_linear_fp8(x, *hit)
         return F.linear(x, self.weight)
 
     def extra_repr(self):
@@ -691,6 +694,7 @@ class BasicsTransformerLM(nn.Module):
         graph=False,
         draft=None,
         draft_tokens: int = 4,
+        weights=None,
     ) -> torch.Tensor:
         """Autoregressive sampling (``model.py:255-310``) with a working top-k filter (the
         reference's ``masked_fill`` is not in place and its threshold broadcast is wrong for B>1).
@@ -705,6 +709,12 @@ class BasicsTransformerLM(nn.Module):
         cached step is one replay. ``graph=<DecodeGraph>`` reuses a caller-owned graph of this model
         and batch size (its cache is reset and prefilled), which saves the capture per call.
         Sampling stays eager.
+
+        ``weights=qw`` (an ``Fp8DecodeWeights`` of this model, with ``graph=True``): the graph is built
+        with the FP8 weight copy, so every replayed step streams 8-bit weights. The prefill is
+        unchanged and reads the 16-bit weights, as do the sliding-window steps once the window is
+        full. With ``graph=<DecodeGraph>`` the graph's own weights are used; ``weights=`` without a
+        graph raises.
 
         ``draft=<model>``: greedy speculative decoding (``models/speculative.py``): the draft proposes
         ``draft_tokens`` tokens per round and this model verifies them in one chunk step; the output
@@ -721,12 +731,16 @@ class BasicsTransformerLM(nn.Module):
                 raise ValueError("generate(draft=...) is greedy: it needs top_k == 1")
             if not isinstance(graph, bool):
                 raise ValueError("generate(draft=...) takes graph=True or False")
+            if weights is not None:
+                raise ValueError("generate(draft=...) does not take weights=")
             return speculative_generate(self, draft, x, max_new_tokens, draft_tokens, eos_token_id, graph)[0]
 
         if x.dim() == 1:
             x = x.unsqueeze(0)
         orig = x.size(-1)
         cache = dg = None
+        if weights is not None and (graph is False or graph is None):
+            raise ValueError("generate(weights=...) needs graph=True or a DecodeGraph: only graph steps read FP8 weights")
         if graph is not False and graph is not None:
             if not use_cache:
                 raise ValueError("generate(graph=...) needs use_cache=True")
@@ -757,7 +771,7 @@ class BasicsTransformerLM(nn.Module):
                 logits = self.forward_cached(ctx, cache)  # prefill
             elif cache is not None and cache.length + 1 == x.size(1) <= self.context_length:
                 if graph is True and dg is None:
-                    dg = DecodeGraph(self, cache, capture=True)
+                    dg = DecodeGraph(self, cache, capture=True, weights=weights)
                 logits = dg.step(x[:, -1:]) if dg is not None else self.forward_cached(x[:, -1:], cache)
             else:
                 cache = None  # the window is full (and slides from here on): full recomputation

@@ -15,7 +15,8 @@ from .flash_attention import (
 )
 from .rmsnorm import add_rmsnorm, add_rmsnorm_ref, rmsnorm, rmsnorm_ref
 from .rope import rope, rope_ref
-from .skinny import skinny_linear, skinny_linear_ref
+from .skinny import (quantize_fp8_rows, quantize_fp8_rows_, skinny_linear, skinny_linear_fp8, skinny_linear_fp8_ref,
+                     skinny_linear_ref)
 from .swiglu import silu, silu_mul, silu_mul_ref
 
 __all__ = [
@@ -50,7 +51,11 @@ __all__ = [
     "rmsnorm_ref",
     "rope",
     "rope_ref",
+    "quantize_fp8_rows",
+    "quantize_fp8_rows_",
     "skinny_linear",
+    "skinny_linear_fp8",
+    "skinny_linear_fp8_ref",
     "skinny_linear_ref",
     "silu",
     "silu_mul",

@@ -190,3 +190,9 @@ if hasattr(torch.ops.cs336, "gemm_skinny"):  # (absent from libraries built befo
     @register_fake("cs336::gemm_skinny")
     def _gemm_skinny(x, w, out):
         return None
+
+    if hasattr(torch.ops.cs336, "gemm_skinny_w8"):  # (absent from libraries built before the FP8 weights)
+
+        @register_fake("cs336::gemm_skinny_w8")
+        def _gemm_skinny_w8(x, wq, scale, out):
+            return None

@@ -293,19 +293,66 @@ def gemm8_rope(x: torch.Tensor, w: torch.Tensor, cos: torch.Tensor, sin: torch.T
 
 SKINNY_MAX_M = 16  # rows the skinny-M kernel takes (one MFMA tile of batch rows)
 _SKINNY = False
+_FP8 = None  # the quantized weights (models/quantized.py) of the innermost skinny_decode(fp8=...)
 
 
 @contextmanager
-def skinny_decode():
+def skinny_decode(fp8=None):
     """While active, :func:`mm_nt` sends calls with at most ``SKINNY_MAX_M`` rows that
     :func:`skinny_ok` takes to the weight-streaming kernel (``csrc/gemm/gemm_skinny.hip``): the
-    M = batch projections of a decode step. Off by default; outside it ``mm_nt`` is unchanged."""
-    global _SKINNY
-    prev, _SKINNY = _SKINNY, True
+    M = batch projections of a decode step. Off by default; outside it ``mm_nt`` is unchanged.
+
+    ``fp8=qw`` (an ``Fp8DecodeWeights``): a call whose ``w`` is in ``qw``'s table runs
+    ``ops.skinny_linear_fp8`` on the quantized copy instead -- the FP8 kernel
+    (``csrc/gemm/gemm_skinny_w8.hip``) at 16 rows or fewer, for every such shape:
+    :func:`skinny_routed`'s exception was measured for the 16-bit kernel against ``torch.mm`` and
+    does not apply to it. A ``w`` that is not in the table takes the path above."""
+    global _SKINNY, _FP8
+    prev, _SKINNY, prev_fp8, _FP8 = _SKINNY, True, _FP8, fp8
     try:
         yield
     finally:
-        _SKINNY = prev
+        _SKINNY, _FP8 = prev, prev_fp8
+
+
+def fp8_lookup(w: torch.Tensor):
+    """``(wq, scale)`` for the 16-bit weight ``w`` inside ``skinny_decode(fp8=qw)`` when ``qw`` holds
+    its quantized copy, else None."""
+    return None if _FP8 is None else _FP8.lookup(w)
+
+
+def skinny_w8_ok(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> bool:
+    """Whether ``cs336::gemm_skinny_w8`` takes ``(x @ wq.T) * scale``: GPU bf16 / fp16 ``x`` of at most
+    16 rows, e4m3 ``wq``, fp32 contiguous ``scale``, K % 16 == 0, row-major operands with 16-B aligned
+    rows (``wq`` rows at least K apart)."""
+    return (
+        x.is_cuda
+        and wq.is_cuda
+        and scale.is_cuda
+        and x.dtype in (torch.bfloat16, torch.float16)
+        and wq.dtype in (torch.float8_e4m3fn, torch.uint8)
+        and scale.dtype == torch.float32
+        and x.dim() == 2
+        and wq.dim() == 2
+        and scale.dim() == 1
+        and x.shape[1] == wq.shape[1]
+        and scale.shape[0] == wq.shape[0]
+        and scale.is_contiguous()
+        and _aligned_rows(x)
+        and x.stride(0) >= 0
+        and wq.stride(1) == 1
+        and wq.stride(0) % 16 == 0
+        and wq.data_ptr() % 16 == 0
+        and (wq.shape[0] == 1 or wq.stride(0) >= wq.shape[1])
+        and ext_available()
+        and ops().gemm_skinny_w8_ok(x.shape[0], wq.shape[0], x.shape[1], x.element_size())
+    )
+
+
+def skinny_w8_mm(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    out = torch.empty(x.shape[0], wq.shape[0], device=x.device, dtype=x.dtype)
+    ops().gemm_skinny_w8(x, wq, scale, out)
+    return out
 
 
 def skinny_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
@@ -343,6 +390,12 @@ def skinny_mm(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 
 def mm_nt(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """``x @ w.T`` (forward of a linear layer; the input gradient through a Wᵀ shadow)."""
+    if _FP8 is not None:
+        hit = _FP8.lookup(w)
+        if hit is not None:
+            from .skinny import skinny_linear_fp8
+
+            return skinny_linear_fp8(x, *hit)
     if (_SKINNY and x.shape[0] <= SKINNY_MAX_M and skinny_routed(x.shape[0], w.shape[0], x.shape[1])
             and skinny_ok(x, w)):
         return skinny_mm(x, w)

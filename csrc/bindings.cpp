@@ -1635,7 +1635,58 @@ void gemm_skinny(const at::Tensor& x, const at::Tensor& w, at::Tensor& out) {
   cs336::gemm_skinny(p, to_dtype(x), stream());
 }
 
+// ------------------------------------------------------------------------------------------
+// FP8 weight-only skinny-M GEMM (csrc/gemm/gemm_skinny_w8.hip):
+// out[M,N] = (x[M,K] · wq[N,K]ᵀ) * scale[N], wq e4m3 (or its uint8 view), x / out bf16 or fp16
+// ------------------------------------------------------------------------------------------
+bool gemm_skinny_w8_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
+  return cs336::gemm_skinny_w8_ok(M, N, K, elem_size);
+}
+
+void gemm_skinny_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
+  check_cuda(x, "x");
+  check_cuda(wq, "wq");
+  check_cuda(scale, "scale");
+  check_cuda(out, "out");
+  TORCH_CHECK(x.dim() == 2 && wq.dim() == 2 && out.dim() == 2 && scale.dim() == 1,
+              "cs336: gemm_skinny_w8 takes x (M, K), wq (N, K), scale (N,), out (M, N)");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf, "cs336: gemm_skinny_w8 takes bf16 / fp16 x");
+  TORCH_CHECK(out.scalar_type() == x.scalar_type(), "cs336: gemm_skinny_w8 x / out dtype mismatch");
+  TORCH_CHECK(wq.scalar_type() == at::kFloat8_e4m3fn || wq.scalar_type() == at::kByte,
+              "cs336: gemm_skinny_w8 takes wq as float8_e4m3fn or its uint8 view");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat, "cs336: gemm_skinny_w8 scale must be fp32");
+  TORCH_CHECK(wq.device() == x.device() && scale.device() == x.device() && out.device() == x.device(),
+              "cs336: gemm_skinny_w8 tensors must be on one device");
+  const int64_t M = x.size(0), K = x.size(1), N = wq.size(0);
+  TORCH_CHECK(wq.size(1) == K && out.size(0) == M && out.size(1) == N, "cs336: gemm_skinny_w8 shape mismatch");
+  TORCH_CHECK(scale.size(0) == N && scale.is_contiguous(), "cs336: gemm_skinny_w8 scale must be contiguous with N = ", N, " elements");
+  TORCH_CHECK(M >= 1 && M <= 16, "cs336: gemm_skinny_w8 takes 1 <= M <= 16 (got ", M, ")");
+  TORCH_CHECK(K >= 16 && K % 16 == 0, "cs336: gemm_skinny_w8 needs K % 16 == 0 (got ", K, ")");
+  TORCH_CHECK(cs336::gemm_skinny_w8_ok(M, N, K, x.element_size()), "cs336: gemm_skinny_w8 extents exceed the kernel's 32-bit row / k indices");
+  TORCH_CHECK(x.stride(1) == 1 && wq.stride(1) == 1 && out.stride(1) == 1, "cs336: gemm_skinny_w8 operands must have a contiguous last dim");
+  TORCH_CHECK(x.stride(0) % 8 == 0 && (M == 1 || x.stride(0) >= 0), "cs336: gemm_skinny_w8 x row stride must be a non-negative multiple of 8");
+  TORCH_CHECK(wq.stride(0) % 16 == 0 && (N == 1 || wq.stride(0) >= K), "cs336: gemm_skinny_w8 wq row stride must be a multiple of 16, at least K");
+  TORCH_CHECK(M == 1 || out.stride(0) >= N, "cs336: gemm_skinny_w8 out rows must not overlap");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(x.data_ptr()) % 16) == 0 && (reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16) == 0,
+              "cs336: gemm_skinny_w8 x and wq must be 16-byte aligned");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(out.data_ptr()) % 2) == 0, "cs336: gemm_skinny_w8 out must be element aligned");
+  c10::DeviceGuard g(x.device());
+  cs336::SkinnyW8Params p;
+  p.x = x.data_ptr();
+  p.wq = wq.data_ptr();
+  p.scale = scale.data_ptr<float>();
+  p.out = out.data_ptr();
+  p.ldx = M == 1 ? 0 : x.stride(0);
+  p.ldw = N == 1 ? 0 : wq.stride(0);
+  p.ldo = M == 1 ? 0 : out.stride(0);
+  p.M = (int)M; p.N = (int)N; p.K = (int)K;
+  p.vec_out = (reinterpret_cast<uintptr_t>(out.data_ptr()) % 8) == 0 && p.ldo % 4 == 0;
+  cs336::gemm_skinny_w8(p, to_dtype(x), stream());
+}
+
 TORCH_LIBRARY(cs336, m) {
+  m.def("gemm_skinny_w8(Tensor x, Tensor wq, Tensor scale, Tensor(a!) out) -> ()");
+  m.def("gemm_skinny_w8_ok(int M, int N, int K, int elem_size) -> bool", &gemm_skinny_w8_ok);
   m.def("gemm_skinny(Tensor x, Tensor w, Tensor(a!) out) -> ()");
   m.def("gemm_skinny_ok(int M, int N, int K, int elem_size) -> bool", &gemm_skinny_ok);
   m.def(
@@ -1713,6 +1764,7 @@ TORCH_LIBRARY(cs336, m) {
 }
 
 TORCH_LIBRARY_IMPL(cs336, CUDA, m) {
+  m.impl("gemm_skinny_w8", &gemm_skinny_w8);
   m.impl("gemm_skinny", &gemm_skinny);
   m.impl("fa_decode", &fa_decode);
   m.impl("kv_append_rope", &kv_append_rope);

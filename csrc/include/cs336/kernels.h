@@ -320,4 +320,22 @@ bool gemm_skinny_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size);
 void gemm_skinny_plan(int N, int K, int& tn, int& waves);
 void gemm_skinny(const SkinnyParams& p, DType t, hipStream_t s);
 
+// ---- FP8 weight-only skinny-M GEMM for decode (csrc/gemm/gemm_skinny_w8.hip) ----
+// out[M,N] = round(fp32(x[M,K] · q[N,K]ᵀ) * scale[N]), 1 <= M <= 16; x / out bf16 or fp16 (DType), q
+// OCP e4m3 bytes, scale fp32 per W row. ldx / ldo in elements, ldw in bytes; x / q rows 16-B aligned,
+// K % 16 == 0, any N >= 1. Rows >= M, W rows >= N and scale[>= N] are never read.
+struct SkinnyW8Params {
+  const void* x;
+  const void* wq;
+  const float* scale;
+  void* out;
+  int64_t ldx, ldw, ldo;
+  int M, N, K;
+  bool vec_out;  // out rows 8-B aligned: 4 columns per store
+};
+bool gemm_skinny_w8_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size);
+// W tiles per wave (1 / 2 / 4) and waves (K ranges) per workgroup the launch uses for (N, K)
+void gemm_skinny_w8_plan(int N, int K, int& tn, int& waves);
+void gemm_skinny_w8(const SkinnyW8Params& p, DType t, hipStream_t s);
+
 }  // namespace cs336
