@@ -11,7 +11,7 @@ Skinny-M GEMM table (``--skinny``): ``cs336::gemm_skinny`` (``csrc/gemm/gemm_ski
 projection shapes (qkv, o, w1|w3, w2, lm_head at the GPT-2 vocabulary 50257) of ``xl`` and ``2.7b`` at
 M 1 / 8 / 16, bf16, under the same ``do_bench`` protocol: us and GB/s of W bytes against the achievable
 HBM rate, with ``torch.mm`` on the same operands alongside. ``--fp8`` adds, per row, the FP8 weight-only
-kernel ``cs336::gemm_skinny_w8`` (``csrc/gemm/gemm_skinny_w8.hip``) on ``quantize_fp8_rows(w)``: median and
+kernel ``cs336::gemm_skinny_w8`` (the same file, e4m3 weight format) on ``quantize_fp8_rows(w)``: median and
 q20-q80 over the same 50 flushed calls, GB/s of FP8 bytes, and the ratio to the bf16 skinny kernel of
 the same run.
 

@@ -28,7 +28,8 @@ weight once whatever the row count, and above that the ordinary GEMM path. ``cac
 
 ``weights=qw`` (an ``Fp8DecodeWeights`` of this model, ``models/quantized.py``): the step's projections
 read the FP8 copy of their weights through ``gemm.skinny_decode(fp8=qw)`` -- the FP8 weight-streaming
-kernel (``csrc/gemm/gemm_skinny_w8.hip``) at up to 16 rows -- in the captured, the eager and the
+kernel (the e4m3 weight format of ``csrc/gemm/gemm_skinny.hip``) at up to 16 rows -- in the captured, the
+eager and the
 ``tokens=n`` step alike. Only the steps a ``DecodeGraph`` runs read FP8: the prefill is an ordinary
 ``forward_cached`` on the 16-bit weights. After an in-place weight update call ``qw.refresh()``, which
 requantizes in place; the next replay picks it up.

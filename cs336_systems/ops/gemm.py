@@ -304,7 +304,7 @@ def skinny_decode(fp8=None):
 
     ``fp8=qw`` (an ``Fp8DecodeWeights``): a call whose ``w`` is in ``qw``'s table runs
     ``ops.skinny_linear_fp8`` on the quantized copy instead -- the FP8 kernel
-    (``csrc/gemm/gemm_skinny_w8.hip``) at 16 rows or fewer, for every such shape:
+    (the e4m3 weight format of ``csrc/gemm/gemm_skinny.hip``) at 16 rows or fewer, for every such shape:
     :func:`skinny_routed`'s exception was measured for the 16-bit kernel against ``torch.mm`` and
     does not apply to it. A ``w`` that is not in the table takes the path above."""
     global _SKINNY, _FP8

@@ -10,8 +10,8 @@ backend a missing extension raises.
 FP8 weights (weight-only, W8A16). ``quantize_fp8_rows(w)`` gives ``(wq, scale)``: OCP e4m3 bytes
 (``torch.float8_e4m3fn``) with one fp32 scale per output row, the dequantized weight being
 ``wq[n, k] * scale[n]``. ``skinny_linear_fp8(x, wq, scale)`` is ``(x @ wq.T) * scale`` with the
-activations left in 16 bits: on a GPU, at most 16 rows run ``csrc/gemm/gemm_skinny_w8.hip``, which
-streams half the bytes of the 16-bit kernel, converts W in registers (exactly) and applies the scale
+activations left in 16 bits: on a GPU, at most 16 rows run the e4m3 format of
+``csrc/gemm/gemm_skinny.hip``, which streams half the bytes of the 16-bit format, converts W in registers (exactly) and applies the scale
 to the fp32 sum before its one rounding.
 """
 

@@ -19,6 +19,7 @@
 
 #include "cs336/kernels.h"
 #include "../gemm/gemm8.h"
+#include "../gemm/skinny_plan.h"
 
 namespace {
 
@@ -1595,34 +1596,41 @@ at::Tensor kv_append_rope_chunk(const at::Tensor& qkv, const at::Tensor& cos, co
 int64_t fa_decode_chunk_qt(int64_t n) { return cs336::fa_decode_chunk_qt((int)std::min<int64_t>(n, 1 << 20)); }
 
 // ------------------------------------------------------------------------------------------
-// Skinny-M GEMM for decode (csrc/gemm/gemm_skinny.hip): out[M,N] = x[M,K] · w[N,K]ᵀ, M <= 16
+// Skinny-M GEMM for decode (csrc/gemm/gemm_skinny.hip), M <= 16, x / out bf16 or fp16:
+//   gemm_skinny:    out[M,N] = x[M,K] · w[N,K]ᵀ, w of x's dtype
+//   gemm_skinny_w8: out[M,N] = (x[M,K] · wq[N,K]ᵀ) * scale[N], wq e4m3 (or its uint8 view)
 // ------------------------------------------------------------------------------------------
 bool gemm_skinny_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
-  return cs336::gemm_skinny_ok(M, N, K, elem_size);
+  return cs336::gemm_skinny_ok(cs336::SkinnyFormat::W16, M, N, K, elem_size);
+}
+bool gemm_skinny_w8_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
+  return cs336::gemm_skinny_ok(cs336::SkinnyFormat::E4M3, M, N, K, elem_size);
 }
 
-void gemm_skinny(const at::Tensor& x, const at::Tensor& w, at::Tensor& out) {
+// What the two ops check and fill alike; w's dtype (and scale) is the caller's. `op` and `wn` name the
+// op and its weight operand in the messages; kl is the format's k per 16-byte W load.
+static cs336::SkinnyParams skinny_params(const char* op, const char* wn, cs336::SkinnyFormat f, const at::Tensor& x,
+                                         const at::Tensor& w, at::Tensor& out) {
+  const int64_t kl = cs336::skinny_k_per_load(f);
   check_cuda(x, "x");
-  check_cuda(w, "w");
+  check_cuda(w, wn);
   check_cuda(out, "out");
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2, "cs336: gemm_skinny takes x (M, K), w (N, K), out (M, N)");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf, "cs336: gemm_skinny takes bf16 / fp16");
-  TORCH_CHECK(w.scalar_type() == x.scalar_type() && out.scalar_type() == x.scalar_type(),
-              "cs336: gemm_skinny x / w / out dtype mismatch");
-  TORCH_CHECK(w.device() == x.device() && out.device() == x.device(), "cs336: gemm_skinny tensors must be on one device");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2, "cs336: ", op, " takes x (M, K), ", wn, " (N, K), out (M, N)");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf, "cs336: ", op, " takes bf16 / fp16 x");
+  TORCH_CHECK(out.scalar_type() == x.scalar_type(), "cs336: ", op, " x / out dtype mismatch");
+  TORCH_CHECK(w.device() == x.device() && out.device() == x.device(), "cs336: ", op, " tensors must be on one device");
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(w.size(1) == K && out.size(0) == M && out.size(1) == N, "cs336: gemm_skinny shape mismatch");
-  TORCH_CHECK(M >= 1 && M <= 16, "cs336: gemm_skinny takes 1 <= M <= 16 (got ", M, ")");
-  TORCH_CHECK(K >= 8 && K % 8 == 0, "cs336: gemm_skinny needs K % 8 == 0 (got ", K, ")");
-  TORCH_CHECK(cs336::gemm_skinny_ok(M, N, K, x.element_size()), "cs336: gemm_skinny extents exceed the kernel's 32-bit row / k indices");
-  TORCH_CHECK(x.stride(1) == 1 && w.stride(1) == 1 && out.stride(1) == 1, "cs336: gemm_skinny operands must have a contiguous last dim");
-  TORCH_CHECK(x.stride(0) % 8 == 0 && (M == 1 || x.stride(0) >= 0), "cs336: gemm_skinny x row stride must be a non-negative multiple of 8");
-  TORCH_CHECK(w.stride(0) % 8 == 0 && (N == 1 || w.stride(0) >= K), "cs336: gemm_skinny w row stride must be a multiple of 8, at least K");
-  TORCH_CHECK(M == 1 || out.stride(0) >= N, "cs336: gemm_skinny out rows must not overlap");
+  TORCH_CHECK(w.size(1) == K && out.size(0) == M && out.size(1) == N, "cs336: ", op, " shape mismatch");
+  TORCH_CHECK(M >= 1 && M <= 16, "cs336: ", op, " takes 1 <= M <= 16 (got ", M, ")");
+  TORCH_CHECK(K >= kl && K % kl == 0, "cs336: ", op, " needs K % ", kl, " == 0 (got ", K, ")");
+  TORCH_CHECK(cs336::gemm_skinny_ok(f, M, N, K, x.element_size()), "cs336: ", op, " extents exceed the kernel's 32-bit row / k indices");
+  TORCH_CHECK(x.stride(1) == 1 && w.stride(1) == 1 && out.stride(1) == 1, "cs336: ", op, " operands must have a contiguous last dim");
+  TORCH_CHECK(x.stride(0) % 8 == 0 && (M == 1 || x.stride(0) >= 0), "cs336: ", op, " x row stride must be a non-negative multiple of 8");
+  TORCH_CHECK(w.stride(0) % kl == 0 && (N == 1 || w.stride(0) >= K), "cs336: ", op, " ", wn, " row stride must be a multiple of ", kl, ", at least K");
+  TORCH_CHECK(M == 1 || out.stride(0) >= N, "cs336: ", op, " out rows must not overlap");
   TORCH_CHECK((reinterpret_cast<uintptr_t>(x.data_ptr()) % 16) == 0 && (reinterpret_cast<uintptr_t>(w.data_ptr()) % 16) == 0,
-              "cs336: gemm_skinny x and w must be 16-byte aligned");
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(out.data_ptr()) % 2) == 0, "cs336: gemm_skinny out must be element aligned");
-  c10::DeviceGuard g(x.device());
+              "cs336: ", op, " x and ", wn, " must be 16-byte aligned");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(out.data_ptr()) % 2) == 0, "cs336: ", op, " out must be element aligned");
   cs336::SkinnyParams p;
   p.x = x.data_ptr();
   p.w = w.data_ptr();
@@ -1632,56 +1640,29 @@ void gemm_skinny(const at::Tensor& x, const at::Tensor& w, at::Tensor& out) {
   p.ldo = M == 1 ? 0 : out.stride(0);
   p.M = (int)M; p.N = (int)N; p.K = (int)K;
   p.vec_out = (reinterpret_cast<uintptr_t>(out.data_ptr()) % 8) == 0 && p.ldo % 4 == 0;
-  cs336::gemm_skinny(p, to_dtype(x), stream());
+  p.scale = nullptr;
+  return p;
 }
 
-// ------------------------------------------------------------------------------------------
-// FP8 weight-only skinny-M GEMM (csrc/gemm/gemm_skinny_w8.hip):
-// out[M,N] = (x[M,K] · wq[N,K]ᵀ) * scale[N], wq e4m3 (or its uint8 view), x / out bf16 or fp16
-// ------------------------------------------------------------------------------------------
-bool gemm_skinny_w8_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
-  return cs336::gemm_skinny_w8_ok(M, N, K, elem_size);
+void gemm_skinny(const at::Tensor& x, const at::Tensor& w, at::Tensor& out) {
+  TORCH_CHECK(w.scalar_type() == x.scalar_type(), "cs336: gemm_skinny x / w / out dtype mismatch");
+  const cs336::SkinnyParams p = skinny_params("gemm_skinny", "w", cs336::SkinnyFormat::W16, x, w, out);
+  c10::DeviceGuard g(x.device());
+  cs336::gemm_skinny(p, cs336::SkinnyFormat::W16, to_dtype(x), stream());
 }
 
 void gemm_skinny_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
-  check_cuda(x, "x");
-  check_cuda(wq, "wq");
   check_cuda(scale, "scale");
-  check_cuda(out, "out");
-  TORCH_CHECK(x.dim() == 2 && wq.dim() == 2 && out.dim() == 2 && scale.dim() == 1,
-              "cs336: gemm_skinny_w8 takes x (M, K), wq (N, K), scale (N,), out (M, N)");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf, "cs336: gemm_skinny_w8 takes bf16 / fp16 x");
-  TORCH_CHECK(out.scalar_type() == x.scalar_type(), "cs336: gemm_skinny_w8 x / out dtype mismatch");
+  TORCH_CHECK(scale.dim() == 1, "cs336: gemm_skinny_w8 takes x (M, K), wq (N, K), scale (N,), out (M, N)");
   TORCH_CHECK(wq.scalar_type() == at::kFloat8_e4m3fn || wq.scalar_type() == at::kByte,
               "cs336: gemm_skinny_w8 takes wq as float8_e4m3fn or its uint8 view");
   TORCH_CHECK(scale.scalar_type() == at::kFloat, "cs336: gemm_skinny_w8 scale must be fp32");
-  TORCH_CHECK(wq.device() == x.device() && scale.device() == x.device() && out.device() == x.device(),
-              "cs336: gemm_skinny_w8 tensors must be on one device");
-  const int64_t M = x.size(0), K = x.size(1), N = wq.size(0);
-  TORCH_CHECK(wq.size(1) == K && out.size(0) == M && out.size(1) == N, "cs336: gemm_skinny_w8 shape mismatch");
-  TORCH_CHECK(scale.size(0) == N && scale.is_contiguous(), "cs336: gemm_skinny_w8 scale must be contiguous with N = ", N, " elements");
-  TORCH_CHECK(M >= 1 && M <= 16, "cs336: gemm_skinny_w8 takes 1 <= M <= 16 (got ", M, ")");
-  TORCH_CHECK(K >= 16 && K % 16 == 0, "cs336: gemm_skinny_w8 needs K % 16 == 0 (got ", K, ")");
-  TORCH_CHECK(cs336::gemm_skinny_w8_ok(M, N, K, x.element_size()), "cs336: gemm_skinny_w8 extents exceed the kernel's 32-bit row / k indices");
-  TORCH_CHECK(x.stride(1) == 1 && wq.stride(1) == 1 && out.stride(1) == 1, "cs336: gemm_skinny_w8 operands must have a contiguous last dim");
-  TORCH_CHECK(x.stride(0) % 8 == 0 && (M == 1 || x.stride(0) >= 0), "cs336: gemm_skinny_w8 x row stride must be a non-negative multiple of 8");
-  TORCH_CHECK(wq.stride(0) % 16 == 0 && (N == 1 || wq.stride(0) >= K), "cs336: gemm_skinny_w8 wq row stride must be a multiple of 16, at least K");
-  TORCH_CHECK(M == 1 || out.stride(0) >= N, "cs336: gemm_skinny_w8 out rows must not overlap");
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(x.data_ptr()) % 16) == 0 && (reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16) == 0,
-              "cs336: gemm_skinny_w8 x and wq must be 16-byte aligned");
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(out.data_ptr()) % 2) == 0, "cs336: gemm_skinny_w8 out must be element aligned");
-  c10::DeviceGuard g(x.device());
-  cs336::SkinnyW8Params p;
-  p.x = x.data_ptr();
-  p.wq = wq.data_ptr();
+  TORCH_CHECK(scale.device() == x.device(), "cs336: gemm_skinny_w8 tensors must be on one device");
+  cs336::SkinnyParams p = skinny_params("gemm_skinny_w8", "wq", cs336::SkinnyFormat::E4M3, x, wq, out);
+  TORCH_CHECK(scale.size(0) == p.N && scale.is_contiguous(), "cs336: gemm_skinny_w8 scale must be contiguous with N = ", p.N, " elements");
   p.scale = scale.data_ptr<float>();
-  p.out = out.data_ptr();
-  p.ldx = M == 1 ? 0 : x.stride(0);
-  p.ldw = N == 1 ? 0 : wq.stride(0);
-  p.ldo = M == 1 ? 0 : out.stride(0);
-  p.M = (int)M; p.N = (int)N; p.K = (int)K;
-  p.vec_out = (reinterpret_cast<uintptr_t>(out.data_ptr()) % 8) == 0 && p.ldo % 4 == 0;
-  cs336::gemm_skinny_w8(p, to_dtype(x), stream());
+  c10::DeviceGuard g(x.device());
+  cs336::gemm_skinny(p, cs336::SkinnyFormat::E4M3, to_dtype(x), stream());
 }
 
 TORCH_LIBRARY(cs336, m) {

@@ -1,4 +1,6 @@
-// Skinny-M GEMM for decode: y[M,N] = x[M,K] · W[N,K]ᵀ with 1 <= M <= 16 (gfx950, wave64).
+// Skinny-M GEMM for decode: y[M,N] = x[M,K] · W[N,K]ᵀ with 1 <= M <= 16 (gfx950, wave64), W in x's
+// 16-bit type or as FP8 bytes with a scale per row (W8A16):
+//   out[M,N] = round_T( fp32( x[M,K] · q[N,K]ᵀ ) * scale[N] ),  q OCP e4m3.
 //
 // One token per sequence makes every projection of a decode step a GEMM with M = batch rows: the
 // whole cost is reading W once from HBM. The kernel streams W and does nothing else per byte:
@@ -22,12 +24,34 @@
 //   * Edges by clamped addresses, never by branches around loads: W rows >= N read row N-1 and batch
 //     rows >= M read row M-1 (the same cache lines again); their products land in accumulator
 //     rows / columns that are never stored (an MFMA output element depends on its own A row and B
-//     column only). K % 32 != 0: the last k-blocks run one at a time with the 16-B chunks at
-//     k >= K replaced by zeros in both operands.
-#include <algorithm>
-
+//     column only). K not a multiple of the k-block: the last k-blocks run one at a time with the
+//     16-B W chunks at k >= K, and their x, replaced by zeros.
+//
+// What the FP8 format changes (the policy W8 below; everything else is the one kernel) and why:
+//
+//   * A 16-byte W load carries 16 k-values of one row, two MFMAs' worth. Lane (r, g) = (l & 15,
+//     l >> 4) owns k = 16g .. 16g+15 of a 64-k block of W row r (still ONE 16-B load, and a 64-byte
+//     run of the row per instruction) and the same k of batch row r (TWO 16-B loads of x, 32
+//     contiguous bytes). The first MFMA takes the low 8 k of both, the second the high 8: the MFMA
+//     sums over its 32 k-slots and does not care which k sits in which slot as long as A and B agree.
+//   * W is converted in registers to x's type by v_cvt_scalef32_pk_{bf16,f16}_fp8 with scale 1.0: two
+//     values per VALU instruction, 8 per W load, beside 2 MFMAs. Every e4m3 value is exact in bf16
+//     and in fp16, so the conversion adds no error. The per-row scale multiplies the fp32 sum once in
+//     the epilogue, after the in-workgroup reduction and before the one rounding to T; scale rows
+//     >= N read scale[N-1], like the W rows.
+//
+// Plan (gemm_skinny_plan, skinny_plan.h). TN keeps the same thresholds in both formats, 4 / 2 / 1 at
+// >= 512 / >= 256 / fewer tiles: they come from how many workgroups it takes to pull from every HBM
+// channel, which counts tiles, not bytes. U (k-blocks per register set) is 4 / 4 / 8 in both, so a
+// set holds the same TN x U 16-B W loads per lane -- the same bytes in flight per wave, which is what
+// hides HBM latency -- and in FP8 covers twice the k. x per set is then 2U loads, twice the 16-bit
+// format's registers; the TN = 1 configuration (2 x 96 fragment VGPRs) still fits the 256 that 8 waves
+// of a workgroup leave each wave. Waves: up to 4 / 8 / 8, at most one per full register set of K,
+// aiming at 2048 waves on the chip. With half the bytes per row a given K has half the register sets
+// in FP8, so short-K weights run fewer, equally loaded waves than in bf16.
 #include "cs336/common.h"
 #include "cs336/kernels.h"
+#include "skinny_plan.h"
 
 namespace cs336 {
 namespace {
@@ -37,27 +61,71 @@ typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
-template <typename T> struct Mma;
-template <> struct Mma<BF16> {
-  static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
+// Act<T>::mma: one MFMA; Act<T>::lo / hi: the low / high two e4m3 bytes of a dword as a packed pair
+// of T (exact)
+template <typename T> struct Act;
+template <> struct Act<BF16> {
+  static __device__ __forceinline__ f32x4 mma(u32x4 a, u32x4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
   }
+  static __device__ __forceinline__ uint32_t lo(uint32_t d) {
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d, 1.0f, false));
+  }
+  static __device__ __forceinline__ uint32_t hi(uint32_t d) {
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d, 1.0f, true));
+  }
 };
-template <> struct Mma<F16> {
-  static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
+template <> struct Act<F16> {
+  static __device__ __forceinline__ f32x4 mma(u32x4 a, u32x4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ uint32_t lo(uint32_t d) {
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(d, 1.0f, false));
+  }
+  static __device__ __forceinline__ uint32_t hi(uint32_t d) {
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(d, 1.0f, true));
+  }
+};
+
+// Weight formats, on activations of type T. storage: W's element, the unit of ldw and of k offsets
+// into a W row; kPerLoad: k per 16-byte W load (8 / 16); kXChunks: 16-B x loads that cover the same k;
+// mma: one W load times its x chunks into the accumulator; kRowScale: the epilogue multiplies by
+// scale[n].
+template <typename T> struct W16 {
+  typedef T act;
+  typedef uint16_t storage;
+  static constexpr SkinnyFormat kFormat = SkinnyFormat::W16;
+  static constexpr int kPerLoad = skinny_k_per_load(kFormat), kXChunks = 1;
+  static constexpr bool kRowScale = false;
+  static __device__ __forceinline__ f32x4 mma(u32x4 w, const u32x4 (&x)[1], f32x4 acc) { return Act<T>::mma(w, x[0], acc); }
+};
+template <typename T> struct W8 {
+  typedef T act;
+  typedef uint8_t storage;
+  static constexpr SkinnyFormat kFormat = SkinnyFormat::E4M3;
+  static constexpr int kPerLoad = skinny_k_per_load(kFormat), kXChunks = 2;
+  static constexpr bool kRowScale = true;
+  static __device__ __forceinline__ f32x4 mma(u32x4 w, const u32x4 (&x)[2], f32x4 acc) {
+    const u32x4 w0 = u32x4{Act<T>::lo(w[0]), Act<T>::hi(w[0]), Act<T>::lo(w[1]), Act<T>::hi(w[1])};
+    const u32x4 w1 = u32x4{Act<T>::lo(w[2]), Act<T>::hi(w[2]), Act<T>::lo(w[3]), Act<T>::hi(w[3])};
+    acc = Act<T>::mma(w0, x[0], acc);
+    return Act<T>::mma(w1, x[1], acc);
   }
 };
 
 __device__ __forceinline__ u32x4 ld16(const uint16_t* p) { return *reinterpret_cast<const u32x4*>(p); }
-__device__ __forceinline__ u32x4 ld16_nt(const uint16_t* p) {
+template <typename S>
+__device__ __forceinline__ u32x4 ld16_nt(const S* p) {
   return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
 }
 
-// TN: W tiles (16 rows each) per wave, sharing one x fragment; U: k-blocks (32 k) per register set;
-// MAXW: most waves (K ranges) per workgroup.
-template <typename T, int TN, int U, int MAXW>
+// F: weight format; TN: W tiles (16 rows each) per wave, sharing one x fragment; U: k-blocks (4 W
+// loads of k: 32 / 64) per register set; MAXW: most waves (K ranges) per workgroup.
+template <typename F, int TN, int U, int MAXW>
 __global__ __launch_bounds__(64 * MAXW) void gemm_skinny_kernel(const SkinnyParams p) {
+  typedef typename F::act T;
+  typedef typename F::storage WS;
+  constexpr int KL = F::kPerLoad, KB = 4 * KL, XC = F::kXChunks;
   __shared__ f32x4 red[MAXW * TN * 64];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -65,11 +133,11 @@ __global__ __launch_bounds__(64 * MAXW) void gemm_skinny_kernel(const SkinnyPara
   const int r = lane & 15, g = lane >> 4;
   const int n0 = (int)blockIdx.x * (16 * TN);
 
-  const uint16_t* wrow[TN];
+  const WS* wrow[TN];
 #pragma unroll
   for (int t = 0; t < TN; ++t)
-    wrow[t] = static_cast<const uint16_t*>(p.w) + (int64_t)min(n0 + 16 * t + r, p.N - 1) * p.ldw + 8 * g;
-  const uint16_t* xrow = static_cast<const uint16_t*>(p.x) + (int64_t)min(r, p.M - 1) * p.ldx + 8 * g;
+    wrow[t] = static_cast<const WS*>(p.w) + (int64_t)min(n0 + 16 * t + r, p.N - 1) * p.ldw + KL * g;
+  const uint16_t* xrow = static_cast<const uint16_t*>(p.x) + (int64_t)min(r, p.M - 1) * p.ldx + KL * g;
 
   f32x4 acc[TN];
 #pragma unroll
@@ -77,26 +145,28 @@ __global__ __launch_bounds__(64 * MAXW) void gemm_skinny_kernel(const SkinnyPara
 
   struct Frag {
     u32x4 w[TN][U];
-    u32x4 x[U];
+    u32x4 x[U][XC];
   };
   auto load = [&](Frag& f, int it) {
-    const int k = it * (32 * U);
-#pragma unroll
-    for (int u = 0; u < U; ++u) f.x[u] = ld16(xrow + k + 32 * u);
+    const int k = it * (KB * U);
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
-      for (int t = 0; t < TN; ++t) f.w[t][u] = ld16_nt(wrow[t] + k + 32 * u);
+      for (int h = 0; h < XC; ++h) f.x[u][h] = ld16(xrow + k + KB * u + 8 * h);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int t = 0; t < TN; ++t) f.w[t][u] = ld16_nt(wrow[t] + k + KB * u);
   };
   auto mma = [&](const Frag& f) {
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
-      for (int t = 0; t < TN; ++t) acc[t] = Mma<T>::run(f.w[t][u], f.x[u], acc[t]);
+      for (int t = 0; t < TN; ++t) acc[t] = F::mma(f.w[t][u], f.x[u], acc[t]);
   };
 
   // full register sets [it0, it1) of this wave's K range
-  const int nfull = p.K / (32 * U);
+  const int nfull = p.K / (KB * U);
   const int it0 = nfull * wave / nw, it1 = nfull * (wave + 1) / nw;  // nfull < 2^25, waves <= 8
   Frag fa, fb;
   int it = it0;
@@ -110,20 +180,24 @@ __global__ __launch_bounds__(64 * MAXW) void gemm_skinny_kernel(const SkinnyPara
   if (it < it1) mma(fa);
 
   // the k-blocks after the last full set (fewer than U, plus a partial one), dealt round-robin
-  const int kt0 = nfull * (32 * U);
-  const int ntail = (p.K - kt0 + 31) / 32;
+  const int kt0 = nfull * (KB * U);
+  const int ntail = (p.K - kt0 + KB - 1) / KB;
   for (int j = wave; j < ntail; j += nw) {
-    const int k = kt0 + 32 * j;
-    const bool ok = k + 8 * g < p.K;  // K % 8 == 0: a 16-B chunk is all inside or all outside
-    const int kk = ok ? k : -8 * g;   // outside: the row's first chunk (valid memory), then zeroed
+    const int k = kt0 + KB * j;
+    const bool ok = k + KL * g < p.K;  // K % KL == 0: a lane's W load is all inside or all outside
+    const int kk = ok ? k : -KL * g;   // outside: the row's first chunk (valid memory), then zeroed
     const u32x4 zero = u32x4{0u, 0u, 0u, 0u};
-    u32x4 xv = ld16(xrow + kk);
-    xv = ok ? xv : zero;
+    u32x4 xv[XC];
+#pragma unroll
+    for (int h = 0; h < XC; ++h) {  // load and select in one body: apart, the selects become branches
+      const u32x4 v = ld16(xrow + kk + 8 * h);
+      xv[h] = ok ? v : zero;
+    }
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
       u32x4 wv = ld16_nt(wrow[t] + kk);
       wv = ok ? wv : zero;
-      acc[t] = Mma<T>::run(wv, xv, acc[t]);
+      acc[t] = F::mma(wv, xv, acc[t]);
     }
   }
 
@@ -136,6 +210,10 @@ __global__ __launch_bounds__(64 * MAXW) void gemm_skinny_kernel(const SkinnyPara
     f32x4 s = red[t * 64 + lane];
     for (int w = 1; w < nw; ++w) s += red[(w * TN + t) * 64 + lane];
     const int n = n0 + 16 * t + 4 * g;
+    if constexpr (F::kRowScale) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[j] *= p.scale[min(n + j, p.N - 1)];
+    }
     if (r < p.M && n < p.N) {
       S* o = static_cast<S*>(p.out) + (int64_t)r * p.ldo + n;
       if (p.vec_out && n + 3 < p.N) {
@@ -151,47 +229,37 @@ __global__ __launch_bounds__(64 * MAXW) void gemm_skinny_kernel(const SkinnyPara
   }
 }
 
-constexpr int kTargetWaves = 2048;  // about 8 waves on each of the 256 CUs
-
-template <typename T, int TN, int U, int MAXW>
+template <typename F, int TN>
 void launch(const SkinnyParams& p, int waves, hipStream_t s) {
-  const int tiles = (p.N + 15) / 16, wgs = (tiles + TN - 1) / TN;
-  hipLaunchKernelGGL((gemm_skinny_kernel<T, TN, U, MAXW>), dim3(wgs), dim3(64 * waves), 0, s, p);
+  hipLaunchKernelGGL((gemm_skinny_kernel<F, TN, skinny_u(TN), skinny_maxw(TN)>), dim3(skinny_workgroups(p.N, TN)),
+                     dim3(64 * waves), 0, s, p);
 }
 
-template <typename T>
+template <typename F>
 void dispatch(const SkinnyParams& p, hipStream_t s) {
   int tn, waves;
-  gemm_skinny_plan(p.N, p.K, tn, waves);
-  // the file's 3 configurations per dtype (tests/test_skinny_resources.py counts them)
-  if (tn == 4) launch<T, 4, 4, 4>(p, waves, s);
-  else if (tn == 2) launch<T, 2, 4, 8>(p, waves, s);
-  else launch<T, 1, 8, 8>(p, waves, s);
+  gemm_skinny_plan(F::kFormat, p.N, p.K, tn, waves);
+  // the file's 3 configurations per format and dtype (tests/test_skinny_resources.py counts them)
+  if (tn == 4) launch<F, 4>(p, waves, s);
+  else if (tn == 2) launch<F, 2>(p, waves, s);
+  else launch<F, 1>(p, waves, s);
 }
 
 }  // namespace
 
-void gemm_skinny_plan(int N, int K, int& tn, int& waves) {
-  const int tiles = (N + 15) / 16;
-  tn = tiles >= 512 ? 4 : (tiles >= 256 ? 2 : 1);
-  const int u = tn == 1 ? 8 : 4, maxw = tn == 4 ? 4 : 8;
-  const int wgs = (tiles + tn - 1) / tn;
-  const int nfull = K / (32 * u);
-  const int want = (kTargetWaves + wgs - 1) / wgs;
-  waves = std::max(1, std::min(maxw, std::min(want, nfull)));
-}
-
-bool gemm_skinny_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
-  // 32-bit row / k indices in the kernel (row offsets are 64-bit): N + 64 and K + 256 must fit
-  return elem_size == 2 && M >= 1 && M <= 16 && N >= 1 && N < (int64_t)1 << 30 && K >= 8 && K % 8 == 0 &&
+bool gemm_skinny_ok(SkinnyFormat f, int64_t M, int64_t N, int64_t K, int64_t elem_size) {
+  // 32-bit row / k indices in the kernel (row offsets are 64-bit): N + 64 and K + 8 k-blocks must fit
+  const int kl = skinny_k_per_load(f);
+  return elem_size == 2 && M >= 1 && M <= 16 && N >= 1 && N < (int64_t)1 << 30 && K >= kl && K % kl == 0 &&
          K < (int64_t)1 << 30;
 }
 
-void gemm_skinny(const SkinnyParams& p, DType t, hipStream_t s) {
-  if (t == DType::BF16) dispatch<BF16>(p, s);
-  else if (t == DType::F16) dispatch<F16>(p, s);
+void gemm_skinny(const SkinnyParams& p, SkinnyFormat f, DType t, hipStream_t s) {
+  const bool w8 = f == SkinnyFormat::E4M3;
+  if (t == DType::BF16) w8 ? dispatch<W8<BF16>>(p, s) : dispatch<W16<BF16>>(p, s);
+  else if (t == DType::F16) w8 ? dispatch<W8<F16>>(p, s) : dispatch<W16<F16>>(p, s);
   else {
-    fprintf(stderr, "cs336: gemm_skinny takes bf16 / fp16 only\n");
+    fprintf(stderr, "cs336: gemm_skinny takes bf16 / fp16 activations only\n");
     abort();
   }
   CS336_HIP_CHECK(hipGetLastError());

@@ -304,38 +304,23 @@ struct AppendChunkParams {
 };
 void kv_append_rope_chunk(const AppendChunkParams& p, DType t, hipStream_t s);
 
-// ---- skinny-M GEMM for decode (csrc/gemm/gemm_skinny.hip) ----
-// out[M,N] = x[M,K] · w[N,K]ᵀ, 1 <= M <= 16, bf16 / fp16 with fp32 accumulation. Row strides in
-// elements; x / w rows 16-B aligned, K % 8 == 0, any N >= 1. Rows >= M, W rows >= N are never read.
+// ---- skinny-M GEMM for decode, 16-bit or FP8 weights (csrc/gemm/gemm_skinny.hip) ----
+// W16:  out[M,N] = x[M,K] · w[N,K]ᵀ, w of x's type.
+// E4M3: out[M,N] = round(fp32(x[M,K] · w[N,K]ᵀ) * scale[N]), w OCP e4m3 bytes, scale fp32 per W row.
+// 1 <= M <= 16; x / out bf16 or fp16 (DType) with fp32 accumulation. ldx / ldo in elements, ldw in
+// elements of W's storage (16-bit words / bytes); x / w rows 16-B aligned, K a multiple of one 16-byte
+// W load (8 / 16), any N >= 1. Rows >= M, W rows >= N and scale[>= N] are never read.
+enum class SkinnyFormat { W16, E4M3 };
 struct SkinnyParams {
   const void* x;
   const void* w;
   void* out;
   int64_t ldx, ldw, ldo;
   int M, N, K;
-  bool vec_out;  // out rows 8-B aligned: 4 columns per store
+  bool vec_out;        // out rows 8-B aligned: 4 columns per store
+  const float* scale;  // E4M3 only; W16 never reads it
 };
-bool gemm_skinny_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size);
-// W tiles per wave (1 / 2 / 4) and waves (K ranges) per workgroup the launch uses for (N, K)
-void gemm_skinny_plan(int N, int K, int& tn, int& waves);
-void gemm_skinny(const SkinnyParams& p, DType t, hipStream_t s);
-
-// ---- FP8 weight-only skinny-M GEMM for decode (csrc/gemm/gemm_skinny_w8.hip) ----
-// out[M,N] = round(fp32(x[M,K] · q[N,K]ᵀ) * scale[N]), 1 <= M <= 16; x / out bf16 or fp16 (DType), q
-// OCP e4m3 bytes, scale fp32 per W row. ldx / ldo in elements, ldw in bytes; x / q rows 16-B aligned,
-// K % 16 == 0, any N >= 1. Rows >= M, W rows >= N and scale[>= N] are never read.
-struct SkinnyW8Params {
-  const void* x;
-  const void* wq;
-  const float* scale;
-  void* out;
-  int64_t ldx, ldw, ldo;
-  int M, N, K;
-  bool vec_out;  // out rows 8-B aligned: 4 columns per store
-};
-bool gemm_skinny_w8_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size);
-// W tiles per wave (1 / 2 / 4) and waves (K ranges) per workgroup the launch uses for (N, K)
-void gemm_skinny_w8_plan(int N, int K, int& tn, int& waves);
-void gemm_skinny_w8(const SkinnyW8Params& p, DType t, hipStream_t s);
+bool gemm_skinny_ok(SkinnyFormat f, int64_t M, int64_t N, int64_t K, int64_t elem_size);
+void gemm_skinny(const SkinnyParams& p, SkinnyFormat f, DType t, hipStream_t s);
 
 }  // namespace cs336

@@ -13,12 +13,16 @@
 //    at the addresses the kernels compute: row_offsets (fa_bwd_common.h), tr_offsets and
 //    lds_tr_addr (fa_common.h), which must agree with lds_off and with each other;
 //  * stream_k_mode / macro_tile_area (tensile_names.h): the Tensile name parsing behind the
-//    concurrency-safe GEMM selection.
+//    concurrency-safe GEMM selection;
+//  * gemm_skinny_plan (gemm/skinny_plan.h): for both weight formats the decode GEMM's plan picks the
+//    tile count per wave at its thresholds, a wave count within the kernel's MAXW and the full register
+//    sets of K, and a grid that covers every tile; a table pins the plans of the model's shapes.
 #include <cstdio>
 #include <set>
 #include <vector>
 
 #include "../gemm/gemm_common.h"
+#include "../gemm/skinny_plan.h"
 #include "cs336/tensile_names.h"
 #include "fa_bwd_common.h"
 
@@ -179,7 +183,51 @@ static void check_row_perm() {
       CHECK(row_perm(4 * row_perm_src_chunk(c) + u) == 4 * c + u, "DMA chunk %d element %d", c, u);
 }
 
+// U (k-blocks per register set) and MAXW are written out here as the kernel's three configurations
+// have them (TN 4: 4, 4; TN 2: 4, 8; TN 1: 8, 8), the k-block as 4 W loads of 8 / 16 k
+static void check_skinny_plan() {
+  std::vector<int> ns;
+  for (int n = 1; n <= 8300; ++n) ns.push_back(n);  // every N: 4095 / 4096 and 8176 / 8177 are the tile thresholds
+  ns.push_back(50257);
+  long checked = 0;
+  for (SkinnyFormat f : {SkinnyFormat::W16, SkinnyFormat::E4M3}) {
+    const int unit = f == SkinnyFormat::W16 ? 8 : 16, kblock = 4 * unit;
+    const char* fn = f == SkinnyFormat::W16 ? "16-bit" : "fp8";
+    for (int N : ns)
+      for (int K = unit; K <= 10240; K += unit) {
+        int tn = -1, waves = -1;
+        gemm_skinny_plan(f, N, K, tn, waves);
+        const int tiles = (N + 15) / 16;
+        CHECK(tn == (tiles >= 512 ? 4 : tiles >= 256 ? 2 : 1), "skinny plan %s N=%d K=%d: tn %d for %d tiles", fn, N, K, tn, tiles);
+        if (tn != 1 && tn != 2 && tn != 4) continue;
+        const int u = tn == 1 ? 8 : 4;
+        CHECK(waves >= 1 && waves <= (tn == 4 ? 4 : 8), "skinny plan %s N=%d K=%d: %d waves at tn %d", fn, N, K, waves, tn);
+        CHECK(waves <= std::max(1, K / (kblock * u)), "skinny plan %s N=%d K=%d: %d waves for %d full sets", fn, N, K, waves, K / (kblock * u));
+        const int wgs = skinny_workgroups(N, tn);
+        CHECK(wgs * tn >= tiles && (wgs - 1) * tn < tiles, "skinny plan %s N=%d: %d workgroups x %d for %d tiles", fn, N, wgs, tn, tiles);
+        ++checked;
+      }
+  }
+  // (N, K) -> (tn, waves), 16-bit then fp8, as the two plan functions gave them before they became one
+  // (0, 0: K is no multiple of 16)
+  const int table[][6] = {{48, 8240, 1, 8, 1, 8},   {4100, 1616, 2, 8, 2, 6},  {4800, 1600, 2, 8, 2, 6},  {1600, 1600, 1, 6, 1, 3},
+                          {12800, 1600, 4, 4, 4, 4}, {50257, 1600, 4, 3, 4, 3}, {50257, 64, 4, 1, 4, 1},   {2560, 10240, 1, 8, 1, 8},
+                          {8177, 512, 4, 4, 4, 2},  {8176, 512, 2, 4, 2, 2},   {1, 8, 1, 1, 0, 0},        {1, 16, 1, 1, 1, 1},
+                          {6400, 1600, 2, 8, 2, 6}, {1600, 6400, 1, 8, 1, 8},  {4096, 256, 2, 2, 2, 1},   {4081, 1024, 2, 8, 2, 4},
+                          {4080, 1024, 1, 4, 1, 2}, {17, 48, 1, 1, 1, 1}};
+  for (const auto& r : table)
+    for (int w8 = 0; w8 < 2; ++w8) {
+      if (!r[2 + 2 * w8]) continue;
+      int tn = -1, waves = -1;
+      gemm_skinny_plan(w8 ? SkinnyFormat::E4M3 : SkinnyFormat::W16, r[0], r[1], tn, waves);
+      CHECK(tn == r[2 + 2 * w8] && waves == r[3 + 2 * w8], "skinny plan %s (%d, %d): (%d, %d), recorded (%d, %d)", w8 ? "fp8" : "16-bit", r[0],
+            r[1], tn, waves, r[2 + 2 * w8], r[3 + 2 * w8]);
+    }
+  std::printf("skinny plan: %ld (format, N, K) checked\n", checked);
+}
+
 int main() {
+  check_skinny_plan();
   check_row_perm();
   check_tile_order();
   check_gemm_tile_order();

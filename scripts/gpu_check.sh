@@ -54,6 +54,11 @@ for r in json.load(open('gpurun_out/flash4096.json')):
       CS336_LIB=cs336_systems/_native/variants/base/libcs336_hip.so timeout -k 10 240 python -u scripts/gemm8_bitwise.py dump "$dump" 2>&1 && \
       timeout -k 10 240 python -u scripts/gemm8_bitwise.py check "$dump" 2>&1 || { rm -f "$dump"; exit 1; }
       rm -f "$dump" ;;
+    skbits)  # both skinny-M decode GEMM ops on the tests' dispatch shapes, base variant lib vs this tree's lib, bit for bit
+      dump=$(mktemp --suffix .pt)
+      CS336_LIB=cs336_systems/_native/variants/base/libcs336_hip.so timeout -k 10 240 python -u scripts/skinny_bitwise.py dump "$dump" 2>&1 && \
+      timeout -k 10 240 python -u scripts/skinny_bitwise.py check "$dump" 2>&1 || { rm -f "$dump"; exit 1; }
+      rm -f "$dump" ;;
     graphab)  # eager step vs the whole step captured in one HIP graph, same box
       timeout -k 10 900 python scripts/ab.py bench "eager:" "graphs:PYTHONFAULTHANDLER=1:--graphs on" --rounds ${AB_ROUNDS:-2} --steps 10 --timeout 300 > gpurun_out/graphab.log 2>&1 || { tail -30 gpurun_out/graphab.log; exit 1; }
       tail -8 gpurun_out/graphab.log ;;

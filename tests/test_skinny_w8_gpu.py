@@ -1,4 +1,5 @@
-"""The FP8 weight-only skinny-M GEMM kernel (``csrc/gemm/gemm_skinny_w8.hip``, ``cs336::gemm_skinny_w8``)
+"""The FP8 weight-only skinny-M GEMM kernel (the e4m3 weight format of ``csrc/gemm/gemm_skinny.hip``,
+``cs336::gemm_skinny_w8``)
 against an fp64 oracle, with the one comparison rule of ``test_kernel_edges_gpu.py`` (``check``, ``k = 4``):
 ``ref64 = (x.double() @ wq.double().T) * scale.double()`` and the same in plain fp32. Both come from
 the QUANTIZED operands, so the quantization error is not in the comparison; against the 16-bit kernel
