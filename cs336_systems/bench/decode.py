@@ -35,6 +35,18 @@ t in {1, 2, 4, 8, 16}, timed interleaved on one cache (truncated back after ever
 a speculative verify step relative to an ordinary one.
 
     python -m cs336_systems.bench.decode --chunk --arms verify --json profiles/decode_chunk.json
+
+FP8 KV cache (``--kv-fp8``; ``csrc/flash_attn/fa_decode_kv8.hip``, ``fa_decode_chunk_kv8.hip``): every
+kernel row and chunk row also times the same call over the FP8 form of the same K / V (e4m3 rows with
+one fp32 scale per row, written by ``ops.kv_quantize_rows``): median and q20-q80 over the same 50 flushed
+calls, GB/s over the bytes it reads (d + 4 per row), its share of the achievable rate and its ratio to
+the 16-bit kernel of the same row, faster / slower only beyond the q20-q80 spread of both sides. The
+arms ``graph+kv8`` (``generate(..., graph=True, kv_fp8=True)``) and ``graph+fp8+kv8`` (with
+``Fp8DecodeWeights`` as well) report like ``graph``, with the bytes of both caches; ``--kv-fp8`` adds the
+end-to-end point context 4096, B 8, prompt 2048 + 512, where the cache is the larger stream of a step.
+
+    python -m cs336_systems.bench.decode --kv-fp8 --chunk --no-e2e --json profiles/decode_kv8_chunk.json
+    python -m cs336_systems.bench.decode --kv-fp8 --no-sweep --arms graph graph+kv8 graph+fp8+kv8 --json profiles/decode_kv8.json
 """
 
 from __future__ import annotations
@@ -52,7 +64,33 @@ HBM_ACHIEVABLE_GBS = 6300.0  # MI355X achievable HBM read rate
 SPLIT_SWEEP = (1, 2, 4, 8, 16, 32, 64)
 
 
-def kernel_row(B: int, H: int, d: int, kv_len: int, warmup: int = 10, rep: int = 50, sweep: bool = True) -> dict:
+def _kv8_planes(k: torch.Tensor, v: torch.Tensor):
+    """The FP8 form of (B, H, n, d) K / V tensors: byte planes, scale planes and the bytes they hold."""
+    planes = []
+    for x in (k, v):
+        p8 = torch.empty(x.shape, dtype=torch.uint8, device=x.device).view(torch.float8_e4m3fn)
+        sc = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
+        ops.kv_quantize_rows(x, p8, sc)
+        planes.append((p8, sc))
+    (k8, ks), (v8, vs) = planes
+    nbytes = float(sum(t.numel() * t.element_size() for t in (k8, ks, v8, vs)))
+    return k8, v8, ks, vs, nbytes
+
+
+def _kv8_columns(row: dict, base: str, fn, nbytes: float, warmup: int, rep: int) -> None:
+    """Time ``fn`` (the FP8-cache call) into ``row`` beside the 16-bit columns ``{base}_us[_q20|_q80]``."""
+    med, lo, hi = do_bench(fn, warmup=warmup, rep=rep)
+    row["kv8_us"], row["kv8_us_q20"], row["kv8_us_q80"] = med * 1e3, lo * 1e3, hi * 1e3
+    row["kv8_mbytes"] = nbytes / 2**20
+    row["kv8_gbs"] = nbytes / (row["kv8_us"] * 1e-6) / 1e9
+    row["kv8_hbm_frac"] = row["kv8_gbs"] / HBM_ACHIEVABLE_GBS
+    row["kv8_vs_bf16"] = row["kv8_us"] / row[f"{base}_us"]  # below 1: the FP8 cache is faster
+    row["kv8_verdict"] = ("faster" if row["kv8_us_q80"] < row[f"{base}_us_q20"] else
+                          "slower" if row["kv8_us_q20"] > row[f"{base}_us_q80"] else "same")
+
+
+def kernel_row(B: int, H: int, d: int, kv_len: int, warmup: int = 10, rep: int = 50, sweep: bool = True,
+               kv_fp8: bool = False) -> dict:
     dev, dt = "cuda", torch.bfloat16
     torch.manual_seed(0)
     q = torch.randn(B, H, d, device=dev, dtype=dt)
@@ -82,6 +120,17 @@ def kernel_row(B: int, H: int, d: int, kv_len: int, warmup: int = 10, rep: int =
     o, _ = ops.decode_attention(q, k, v, lens)
     ref = ops.naive_attention(q4, k, v, is_causal=False)[:, :, 0]
     row["max_abs_diff_vs_naive"] = (o.float() - ref.float()).abs().max().item()
+    if kv_fp8:
+        med, lo, hi = do_bench(lambda: ops.decode_attention(q, k, v, lens), warmup=warmup, rep=rep)
+        row["bf16_us"], row["bf16_us_q20"], row["bf16_us_q80"] = med * 1e3, lo * 1e3, hi * 1e3  # re-measured beside kv8
+        k8, v8, ks, vs, nbytes = _kv8_planes(k, v)
+        row["kv8_splits"] = int(torch.ops.cs336.fa_decode_kv8_splits(B, H, d, 1, kv_len))
+        row["kv8_key_tile"] = int(torch.ops.cs336.fa_decode_kv8_key_tile(d, 1))
+        _kv8_columns(row, "bf16", lambda: ops.decode_attention(q, k8, v8, lens, k_scale=ks, v_scale=vs), nbytes,
+                     warmup, rep)
+        o8, _ = ops.decode_attention(q, k8, v8, lens, k_scale=ks, v_scale=vs)
+        row["kv8_max_abs_diff_vs_bf16"] = (o8.float() - o.float()).abs().max().item()
+        del k8, v8, ks, vs
     del q, k, v
     torch.cuda.empty_cache()
     return row
@@ -90,7 +139,7 @@ def kernel_row(B: int, H: int, d: int, kv_len: int, warmup: int = 10, rep: int =
 CHUNK_N = (1, 2, 4, 8, 16)
 
 
-def chunk_row(B: int, H: int, d: int, kv_len: int, n: int, warmup: int = 10, rep: int = 50) -> dict:
+def chunk_row(B: int, H: int, d: int, kv_len: int, n: int, warmup: int = 10, rep: int = 50, kv_fp8: bool = False) -> dict:
     dev, dt = "cuda", torch.bfloat16
     torch.manual_seed(0)
     q = torch.randn(B, n, H, d, device=dev, dtype=dt)
@@ -116,6 +165,15 @@ def chunk_row(B: int, H: int, d: int, kv_len: int, n: int, warmup: int = 10, rep
     o, _ = ops.decode_attention_chunk(q, k, v, lens)
     o1, _ = ops.decode_attention(q1[-1], k, v, lens)  # the last query sees every key
     row["max_abs_diff_last_query_vs_decode"] = (o[:, -1].float() - o1.float()).abs().max().item()
+    if kv_fp8:
+        k8, v8, ks, vs, nbytes = _kv8_planes(k, v)
+        row["kv8_splits"] = int(torch.ops.cs336.fa_decode_kv8_splits(B, H, d, n, kv_len))
+        row["kv8_key_tile"] = int(torch.ops.cs336.fa_decode_kv8_key_tile(d, n))
+        _kv8_columns(row, "chunk", lambda: ops.decode_attention_chunk(q, k8, v8, lens, k_scale=ks, v_scale=vs), nbytes,
+                     warmup, rep)
+        o8, _ = ops.decode_attention_chunk(q, k8, v8, lens, k_scale=ks, v_scale=vs)
+        row["kv8_max_abs_diff_vs_bf16"] = (o8.float() - o.float()).abs().max().item()
+        del k8, v8, ks, vs
     del q, k, v
     torch.cuda.empty_cache()
     return row
@@ -219,18 +277,21 @@ def skinny_row(model_size: str, name: str, M: int, N: int, K: int, warmup: int =
 
 
 ARMS = {"cached": dict(use_cache=True), "uncached": dict(use_cache=False), "graph": dict(use_cache=True, graph=True),
-        "graph+fp8": dict(use_cache=True, graph=True)}  # (+ weights=Fp8DecodeWeights(model), built per model)
-ARM_KEYS = {"graph": "cached_graph", "graph+fp8": "cached_graph_fp8"}
+        "graph+fp8": dict(use_cache=True, graph=True),  # (+ weights=Fp8DecodeWeights(model), built per model)
+        "graph+kv8": dict(use_cache=True, graph=True, kv_fp8=True),
+        "graph+fp8+kv8": dict(use_cache=True, graph=True, kv_fp8=True)}  # (+ weights)
+ARM_KEYS = {"graph": "cached_graph", "graph+fp8": "cached_graph_fp8", "graph+kv8": "cached_graph_kv8",
+            "graph+fp8+kv8": "cached_graph_fp8_kv8"}
 
 
-def replay_ms(model, x: torch.Tensor, weights=None, rep: int = 50) -> tuple[float, float, float]:
+def replay_ms(model, x: torch.Tensor, weights=None, rep: int = 50, kv_fp8: bool = False) -> tuple[float, float, float]:
     """Median, q20 and q80 ms of one replayed decode step on a cache holding the prompt ``x`` (HIP
     events around the replay; the cache is truncated back after every step)."""
     from ..models import DecodeGraph
     from ..models.kv_cache import KVCache
 
     B, prompt = x.shape
-    cache = KVCache(model, B)
+    cache = KVCache(model, B, fp8=kv_fp8)
     model.forward_cached(x, cache)
     dg = DecodeGraph(model, cache, capture=True, weights=weights)
     tok, ts = x[:, -1:], []
@@ -257,7 +318,7 @@ def e2e_row(model_size: str, ctx: int, B: int, prompt: int, new: int, arms=("cac
     qw = None
     for arm in arms:
         kw = dict(ARMS[arm])
-        if arm == "graph+fp8":
+        if arm in ("graph+fp8", "graph+fp8+kv8"):
             from ..models import Fp8DecodeWeights
 
             qw = qw or Fp8DecodeWeights(model)
@@ -275,8 +336,16 @@ def e2e_row(model_size: str, ctx: int, B: int, prompt: int, new: int, arms=("cac
         row[f"{name}_tok_s"] = B * new / dt
         row[f"{name}_ms_per_step"] = dt / new * 1e3
         if arm in ARM_KEYS:
-            med, lo, hi = replay_ms(model, x, kw.get("weights"))
+            med, lo, hi = replay_ms(model, x, kw.get("weights"), kv_fp8=kw.get("kv_fp8", False))
             row[f"{name}_replay_ms"], row[f"{name}_replay_ms_q20"], row[f"{name}_replay_ms_q80"] = med, lo, hi
+        if kw.get("kv_fp8") and "kv8_cache_mbytes" not in row:
+            from ..models.kv_cache import KVCache
+
+            attn = model.layers[0].attn
+            dims = (len(model.layers), attn.num_heads, attn.d_k)
+            sizes = [KVCache(dims, 1, max_len=1, device="cuda", dtype=torch.bfloat16, fp8=f).nbytes for f in (False, True)]
+            row["kv_cache_mbytes"], row["kv8_cache_mbytes"] = (s * B * ctx / 2**20 for s in sizes)
+            row["kv8_cache_vs_bf16"] = sizes[1] / sizes[0]
     if "cached_s" in row and "uncached_s" in row:
         row["speedup"] = row["uncached_s"] / row["cached_s"]
     if "cached_s" in row and "cached_graph_s" in row:
@@ -284,6 +353,13 @@ def e2e_row(model_size: str, ctx: int, B: int, prompt: int, new: int, arms=("cac
     if "cached_graph_s" in row and "cached_graph_fp8_s" in row:
         row["fp8_speedup_vs_graph"] = row["cached_graph_s"] / row["cached_graph_fp8_s"]
         row["fp8_replay_vs_graph"] = row["cached_graph_fp8_replay_ms"] / row["cached_graph_replay_ms"]
+    for name in ("cached_graph_kv8", "cached_graph_fp8_kv8"):
+        if "cached_graph_s" in row and f"{name}_s" in row:
+            row[f"{name}_speedup_vs_graph"] = row["cached_graph_s"] / row[f"{name}_s"]
+            row[f"{name}_replay_vs_graph"] = row[f"{name}_replay_ms"] / row["cached_graph_replay_ms"]
+            row[f"{name}_replay_verdict"] = (
+                "faster" if row[f"{name}_replay_ms_q80"] < row["cached_graph_replay_ms_q20"] else
+                "slower" if row[f"{name}_replay_ms_q20"] > row["cached_graph_replay_ms_q80"] else "same")
     del model
     torch.cuda.empty_cache()
     return row
@@ -301,6 +377,9 @@ def main(argv=None):
     ap.add_argument("--model", default="xl")
     ap.add_argument("--skinny", action="store_true", help="the skinny-M GEMM table (xl and 2.7b projections)")
     ap.add_argument("--fp8", action="store_true", help="with --skinny: add the FP8 weight-only kernel to every row")
+    ap.add_argument("--kv-fp8", action="store_true",
+                    help="add the FP8 KV cache kernels to every kernel / chunk row, and the end-to-end point "
+                         "context 4096, B 8, prompt 2048 + 512")
     ap.add_argument("--chunk", action="store_true",
                     help="the multi-token tables: decode_attention_chunk rows instead of the single-token sweep, and "
                          "(with --arms verify) the replayed n-token step; no generate arms")
@@ -323,7 +402,7 @@ def main(argv=None):
                     for B in a.batch:
                         for kv in a.kv_len:
                             for n in CHUNK_N:
-                                r = chunk_row(B, H, d, kv, n, rep=a.rep)
+                                r = chunk_row(B, H, d, kv, n, rep=a.rep, kv_fp8=a.kv_fp8)
                                 out["chunk"].append(r)
                                 print(json.dumps(r), flush=True)
             if "verify" in a.arms:
@@ -343,7 +422,7 @@ def main(argv=None):
             H, d = (int(s) for s in shape.split("x"))
             for B in a.batch:
                 for n in a.kv_len:
-                    r = kernel_row(B, H, d, n, rep=a.rep, sweep=not a.no_sweep)
+                    r = kernel_row(B, H, d, n, rep=a.rep, sweep=not a.no_sweep, kv_fp8=a.kv_fp8)
                     out["kernel"].append(r)
                     print(json.dumps(r), flush=True)
     if a.skinny:
@@ -354,7 +433,10 @@ def main(argv=None):
                     out["skinny"].append(r)
                     print(json.dumps(r), flush=True)
     if not a.no_e2e:
-        for ctx, B, prompt, new in ((512, 1, 128, 384), (512, 8, 128, 384), (4096, 1, 2048, 512)):
+        points = [(512, 1, 128, 384), (512, 8, 128, 384), (4096, 1, 2048, 512)]
+        if a.kv_fp8:
+            points.append((4096, 8, 2048, 512))  # the cache is the larger stream of a step
+        for ctx, B, prompt, new in points:
             r = e2e_row(a.model, ctx, B, prompt, new, arms=a.arms)
             out["e2e"].append(r)
             print(json.dumps(r), flush=True)

@@ -33,6 +33,10 @@ eager and the
 ``tokens=n`` step alike. Only the steps a ``DecodeGraph`` runs read FP8: the prefill is an ordinary
 ``forward_cached`` on the 16-bit weights. After an in-place weight update call ``qw.refresh()``, which
 requantizes in place; the next replay picks it up.
+
+An FP8 cache (``KVCache(fp8=True)``) needs no argument: the graph is tied to its cache, the step appends
+and reads quantized rows (``csrc/flash_attn/fa_decode_kv8.hip``, ``fa_decode_chunk_kv8.hip``) and nothing
+in it synchronizes the host either. ``weights=qw`` and an FP8 cache combine.
 """
 
 from __future__ import annotations

@@ -31,11 +31,11 @@ from .decode_graph import DecodeGraph
 from .kv_cache import KVCache
 
 
-def _new_cache(model, batch: int) -> KVCache:
+def _new_cache(model, batch: int, fp8: bool = False) -> KVCache:
     w = model.lm_head.weight
     dev = w.device.type
     cdt = torch.get_autocast_dtype(dev) if torch.is_autocast_enabled(dev) else w.dtype
-    return KVCache(model, batch, device=w.device, dtype=cdt)
+    return KVCache(model, batch, device=w.device, dtype=cdt, fp8=fp8)
 
 
 def _argmax(logits: torch.Tensor) -> torch.Tensor:
@@ -44,13 +44,15 @@ def _argmax(logits: torch.Tensor) -> torch.Tensor:
 
 @torch.no_grad()
 def speculative_generate(target, draft, x: torch.Tensor, max_new_tokens: int, draft_tokens: int = 4,
-                         eos_token_id: int | None = None, graph: bool = False):
+                         eos_token_id: int | None = None, graph: bool = False, kv_fp8: bool = False):
     """``(tokens, stats)``: the greedy continuation of ``x`` under ``target`` (B, <= max_new_tokens)
     and ``stats = dict(rounds, proposed, accepted)`` -- speculative rounds, draft tokens proposed and
     proposals accepted.
 
     ``graph=True`` (GPU models): the draft's steps replay a ``DecodeGraph(tokens=1)`` and the target's
-    verify step a ``DecodeGraph(tokens=draft_tokens + 1)``; rounds with a shrunk ``k`` run eagerly."""
+    verify step a ``DecodeGraph(tokens=draft_tokens + 1)``; rounds with a shrunk ``k`` run eagerly.
+    ``kv_fp8=True``: both caches are FP8 ones (``KVCache(fp8=True)``); the output is then the greedy
+    decoding of the target over its FP8 cache."""
     if target.lm_head.weight.shape[0] != draft.lm_head.weight.shape[0]:
         raise ValueError("speculative decoding needs one vocabulary: the draft's differs from the target's")
     if draft.context_length < target.context_length:
@@ -77,7 +79,7 @@ def speculative_generate(target, draft, x: torch.Tensor, max_new_tokens: int, dr
     # prefill both caches on the prompt (its last ``window`` tokens); the target's last logits give
     # the first token
     ctx = x[:, -window:] if x.size(1) > window else x
-    tc, dc = _new_cache(target, B), _new_cache(draft, B)
+    tc, dc = _new_cache(target, B, kv_fp8), _new_cache(draft, B, kv_fp8)
     last = _argmax(target.forward_cached(ctx, tc)[:, -1])[:, None]
     if one and int(last) == eos_token_id:
         return x[:, orig:], stats

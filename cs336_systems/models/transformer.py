@@ -374,7 +374,8 @@ class CausalMultiHeadSelfAttention(nn.Module):
         with annotate("out_proj"):
             return self.output_proj(o)
 
-    def forward_cached(self, x3, k_cache, v_cache, start: int, pos=None, kv_len=None, max_kv_len=None) -> torch.Tensor:
+    def forward_cached(self, x3, k_cache, v_cache, start: int, pos=None, kv_len=None, max_kv_len=None,
+                       k_scale=None, v_scale=None) -> torch.Tensor:
         """Attention of ``forward_cached`` (inference only). ``x3`` (B, n, d_model); ``k_cache`` /
         ``v_cache`` this layer's (B, H, max_len, dk) cache views. ``start == 0``: prefill -- the
         ordinary causal attention over the n tokens at positions 0..n-1, whose rotated K and V are
@@ -382,7 +383,10 @@ class CausalMultiHeadSelfAttention(nn.Module):
         new token's slot and RoPE position, ``kv_len = pos + 1`` its key count; or a chunk step
         (n > 1) over the chunk ops: ``pos`` is the slot of the chunk's first token, ``kv_len = pos + n``
         the key count of its last. ``max_kv_len``: the host-side bound of ``kv_len`` that picks the
-        decode kernel's split count (default ``start + n``; a captured step passes a fixed one)."""
+        decode kernel's split count (default ``start + n``; a captured step passes a fixed one).
+        ``k_scale`` / ``v_scale``: this layer's (B, H, max_len) scale views of an FP8 cache
+        (``float8_e4m3fn`` planes): the steps append and read quantized rows, and the prefill, which
+        attends to its own unquantized K / V, stores them through ``ops.kv_quantize_rows``."""
         B, n, _ = x3.shape
         H, dk = self.num_heads, self.d_k
         w = [self.q_proj.weight, self.k_proj.weight, self.v_proj.weight]
@@ -391,31 +395,40 @@ class CausalMultiHeadSelfAttention(nn.Module):
                 qkv = fused.fused_linear(x3, *w)  # one grouped QKV GEMM, (B, n, 3*H*dk)
             else:
                 qkv = torch.cat([self.q_proj(x3), self.k_proj(x3), self.v_proj(x3)], dim=-1)
-        if qkv.dtype != k_cache.dtype:
+        fp8 = k_cache.dtype == torch.float8_e4m3fn
+        if fp8 and (k_scale is None or v_scale is None):
+            raise ValueError("an FP8 KV cache needs its k_scale / v_scale views")
+        sc = dict(k_scale=k_scale, v_scale=v_scale) if fp8 else {}
+        if not fp8 and qkv.dtype != k_cache.dtype:
             raise ValueError(f"KV cache dtype {k_cache.dtype} does not match the compute dtype {qkv.dtype}")
         if start > 0 and n > 1:
             with annotate("kv_append_rope_chunk"):
                 q = ops.kv_append_rope_chunk(qkv, self.positional_encoder.cos, self.positional_encoder.sin, pos,
-                                             k_cache, v_cache)
+                                             k_cache, v_cache, **sc)
             with annotate("decode_attention_chunk"):
                 o, _ = ops.decode_attention_chunk(q, k_cache, v_cache, kv_len,
-                                                  max_kv_len=start + n if max_kv_len is None else max_kv_len)
+                                                  max_kv_len=start + n if max_kv_len is None else max_kv_len, **sc)
             o = o.reshape(B, n, H * dk)
         elif start > 0:
             with annotate("kv_append_rope"):
                 q = ops.kv_append_rope(qkv.view(B, 3 * H * dk), self.positional_encoder.cos, self.positional_encoder.sin,
-                                       pos, k_cache, v_cache)
+                                       pos, k_cache, v_cache, **sc)
             with annotate("decode_attention"):
                 o, _ = ops.decode_attention(q, k_cache, v_cache, kv_len,
-                                            max_kv_len=start + 1 if max_kv_len is None else max_kv_len)
+                                            max_kv_len=start + 1 if max_kv_len is None else max_kv_len, **sc)
             o = o.reshape(B, 1, H * dk)
         else:
             q, k, v = (qkv.view(B, n, 3, H, dk)[:, :, i].transpose(1, 2) for i in range(3))
             with annotate("rope"):
                 q = self.positional_encoder(q, None)
                 k = self.positional_encoder(k, None)
-            k_cache[:, :, :n].copy_(k)
-            v_cache[:, :, :n].copy_(v)
+            if fp8:
+                with annotate("kv_quantize_rows"):
+                    ops.kv_quantize_rows(k, k_cache, k_scale)
+                    ops.kv_quantize_rows(v, v_cache, v_scale)
+            else:
+                k_cache[:, :, :n].copy_(k)
+                v_cache[:, :, :n].copy_(v)
             impl = _ATTN_IMPL
             with annotate("attention"):
                 if impl == "naive" or (impl == "auto" and not x3.is_cuda):
@@ -657,6 +670,10 @@ class BasicsTransformerLM(nn.Module):
         if start > 0:  # once per step, shared by all layers
             pos = cache.lengths
             kv_len = cache.lengths + n
+        ks, vs = getattr(cache, "k_scale", None), getattr(cache, "v_scale", None)
+
+        def scales(i):  # the layer's scale views of an FP8 cache
+            return (None, None) if ks is None else (ks[i], vs[i])
         with annotate("embed"):
             h = self.token_embeddings(x)
         n_layers = len(self.layers)
@@ -664,7 +681,8 @@ class BasicsTransformerLM(nn.Module):
             y = self.layers[0].ln1(h)
             for i, layer in enumerate(self.layers):
                 with annotate(f"layer{i}"):
-                    a = layer.attn.forward_cached(y, cache.k[i], cache.v[i], start, pos, kv_len, max_kv_len)
+                    a = layer.attn.forward_cached(y, cache.k[i], cache.v[i], start, pos, kv_len, max_kv_len,
+                                                  *scales(i))
                     self._reading(layer.ln2)
                     h, y = ops.add_rmsnorm(h, a, layer.ln2.weight, layer.ln2.eps)
                     f = layer.ffn(y)
@@ -675,7 +693,7 @@ class BasicsTransformerLM(nn.Module):
             for i, layer in enumerate(self.layers):
                 with annotate(f"layer{i}"):
                     h = h + layer.attn.forward_cached(layer.ln1(h), cache.k[i], cache.v[i], start, pos, kv_len,
-                                                      max_kv_len)
+                                                      max_kv_len, *scales(i))
                     h = h + layer.ffn(layer.ln2(h))
             y = self.ln_final(h)
         cache.advance(n)
@@ -695,6 +713,7 @@ class BasicsTransformerLM(nn.Module):
         draft=None,
         draft_tokens: int = 4,
         weights=None,
+        kv_fp8: bool = False,
     ) -> torch.Tensor:
         """Autoregressive sampling (``model.py:255-310``) with a working top-k filter (the
         reference's ``masked_fill`` is not in place and its threshold broadcast is wrong for B>1).
@@ -716,12 +735,18 @@ class BasicsTransformerLM(nn.Module):
         full. With ``graph=<DecodeGraph>`` the graph's own weights are used; ``weights=`` without a
         graph raises.
 
+        ``kv_fp8=True`` (with ``use_cache=True``): the cache is an FP8 one (``KVCache(fp8=True)``: e4m3
+        rows with per-row scales, about half the bytes), and with ``draft=`` the draft's cache too. With
+        ``graph=<DecodeGraph>`` the graph's own cache is used, whatever its format.
+
         ``draft=<model>``: greedy speculative decoding (``models/speculative.py``): the draft proposes
         ``draft_tokens`` tokens per round and this model verifies them in one chunk step; the output
         is exactly the greedy one. Needs ``use_cache=True``, ``top_k == 1`` and a bool ``graph``;
         sampling from a draft is not supported."""
         from .decode_graph import DecodeGraph
 
+        if kv_fp8 and not use_cache:
+            raise ValueError("generate(kv_fp8=True) needs use_cache=True")
         if draft is not None:
             from .speculative import speculative_generate
 
@@ -733,7 +758,8 @@ class BasicsTransformerLM(nn.Module):
                 raise ValueError("generate(draft=...) takes graph=True or False")
             if weights is not None:
                 raise ValueError("generate(draft=...) does not take weights=")
-            return speculative_generate(self, draft, x, max_new_tokens, draft_tokens, eos_token_id, graph)[0]
+            return speculative_generate(self, draft, x, max_new_tokens, draft_tokens, eos_token_id, graph,
+                                        kv_fp8=kv_fp8)[0]
 
         if x.dim() == 1:
             x = x.unsqueeze(0)
@@ -764,7 +790,7 @@ class BasicsTransformerLM(nn.Module):
                 w = self.lm_head.weight
                 dev = w.device.type
                 cdt = torch.get_autocast_dtype(dev) if torch.is_autocast_enabled(dev) else w.dtype
-                cache = KVCache(self, x.size(0), device=w.device, dtype=cdt)
+                cache = KVCache(self, x.size(0), device=w.device, dtype=cdt, fp8=kv_fp8)
         for _ in range(max_new_tokens):
             ctx = x[:, -self.context_length :] if x.size(1) > self.context_length else x
             if cache is not None and cache.length == 0:

@@ -5,7 +5,9 @@ from ._ext import backend, ext_available, get_backend, load_error, load_ext, set
 from .adamw import FusedAdamW, clip_grad_norm_, multi_tensor_l2norm
 from .cross_entropy import cross_entropy, cross_entropy_ref
 from .decode import (decode_attention, decode_attention_chunk, decode_attention_chunk_ref, decode_attention_ref,
-                     kv_append_rope, kv_append_rope_chunk, kv_append_rope_chunk_ref, kv_append_rope_ref)
+                     kv_append_rope, kv_append_rope_chunk, kv_append_rope_chunk_kv8_ref, kv_append_rope_chunk_ref,
+                     kv_append_rope_kv8_ref, kv_append_rope_ref, kv_dequantize, kv_quantize_ref, kv_quantize_rows,
+                     kv_quantize_rows_ref)
 from .flash_attention import (
     FlashAttentionHIP,
     FlashAttentionTorch,
@@ -38,8 +40,14 @@ __all__ = [
     "decode_attention_ref",
     "kv_append_rope",
     "kv_append_rope_chunk",
+    "kv_append_rope_chunk_kv8_ref",
     "kv_append_rope_chunk_ref",
+    "kv_append_rope_kv8_ref",
     "kv_append_rope_ref",
+    "kv_dequantize",
+    "kv_quantize_ref",
+    "kv_quantize_rows",
+    "kv_quantize_rows_ref",
     "FlashAttentionHIP",
     "FlashAttentionTorch",
     "FlashAttentionTriton",

@@ -185,6 +185,33 @@ if hasattr(torch.ops.cs336, "fa_decode_chunk"):  # (absent from libraries built 
         return qkv.new_empty((B, qkv.shape[1], H, D))
 
 
+if hasattr(torch.ops.cs336, "fa_decode_kv8"):  # (absent from libraries built before the FP8 KV cache: A/B baselines)
+
+    @register_fake("cs336::fa_decode_kv8")
+    def _fa_decode_kv8(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale, max_kv_len, splits=0):
+        B, H, D = q.shape
+        return q.new_empty((B, H, D)), q.new_empty((B, H), dtype=torch.float32)
+
+    @register_fake("cs336::fa_decode_chunk_kv8")
+    def _fa_decode_chunk_kv8(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale, max_kv_len, splits=0):
+        B, n, H, D = q.shape
+        return q.new_empty((B, n, H, D)), q.new_empty((B, n, H), dtype=torch.float32)
+
+    @register_fake("cs336::kv_append_rope_kv8")
+    def _kv_append_rope_kv8(qkv, cos, sin, pos, k_cache, v_cache, k_scale, v_scale):
+        B, H, _, D = k_cache.shape
+        return qkv.new_empty((B, H, D))
+
+    @register_fake("cs336::kv_append_rope_chunk_kv8")
+    def _kv_append_rope_chunk_kv8(qkv, cos, sin, pos, k_cache, v_cache, k_scale, v_scale):
+        B, H, _, D = k_cache.shape
+        return qkv.new_empty((B, qkv.shape[1], H, D))
+
+    @register_fake("cs336::kv_quantize_rows")
+    def _kv_quantize_rows(x, plane, scale):
+        return None
+
+
 if hasattr(torch.ops.cs336, "gemm_skinny"):  # (absent from libraries built before the decode graph: A/B baselines)
 
     @register_fake("cs336::gemm_skinny")

@@ -22,6 +22,16 @@ is rotated at and written to ``pos[b] + i``, and a token without a slot stores n
 
 The HIP kernels take head dims 32 / 64 / 80 / 128 (the ones the model's fused attention path takes);
 other head dims run the reference. On a GPU with the HIP backend a missing extension raises.
+
+FP8 cache (``csrc/flash_attn/fa_decode_kv8.hip``, ``fa_decode_chunk_kv8.hip``): the four ops also take
+``torch.float8_e4m3fn`` cache planes with the keyword-only ``k_scale`` / ``v_scale`` (B, H, max_len)
+fp32 planes, one scale per cached row: the row is ``bytes * scale[row]``. A row is quantized when it
+is written and never again: ``amax = max |x|`` over its d fp32 values, ``scale = amax / 448`` (1 for
+an all-zero row), ``bytes = RNE(clamp(x / scale, -448, 448))`` -- the clamp before the cast, as in
+``quantize_fp8_rows_``, because e4m3fn turns overflow into the NaN byte. An appended K row is
+quantized from its fp32 rotated value (one rounding, not two through the compute dtype).
+``kv_quantize_rows`` is the prefill's store of whole (B, H, n, d) K / V tensors. q / o stay bf16,
+fp16 or fp32. An FP8 cache without both scales, or scales with any other cache, raise ``ValueError``.
 """
 
 from __future__ import annotations
@@ -34,6 +44,69 @@ from ._ext import ops, use_hip
 from .rope import rope_ref
 
 _DECODE_D = (32, 64, 80, 128)
+_E4M3 = torch.float8_e4m3fn
+FP8_MAX = 448.0  # largest finite e4m3 value
+
+
+def _kv8(k_cache, v_cache, k_scale, v_scale) -> bool:
+    """Whether the caches are the FP8 format; the argument errors of the four ops."""
+    if k_cache.dtype != _E4M3 and v_cache.dtype != _E4M3:
+        if k_scale is not None or v_scale is not None:
+            raise ValueError(f"k_scale / v_scale go with a float8_e4m3fn cache, not {k_cache.dtype}")
+        return False
+    if k_cache.dtype != v_cache.dtype:
+        raise ValueError("k_cache and v_cache must both be float8_e4m3fn")
+    if k_scale is None or v_scale is None:
+        raise ValueError("a float8_e4m3fn cache needs k_scale and v_scale")
+    for s, c in ((k_scale, k_cache), (v_scale, v_cache)):
+        if s.dtype != torch.float32 or tuple(s.shape) != tuple(c.shape[:-1]):
+            raise ValueError("k_scale / v_scale must be fp32 (B, H, max_len) planes of the caches")
+    return True
+
+
+def _scale_layout_ok(s: torch.Tensor) -> bool:
+    return s.stride(-1) == 1 and s.data_ptr() % 4 == 0
+
+
+def kv_quantize_ref(x):
+    """Rows ``x`` (..., d) -> e4m3 bytes (..., d) and fp32 scales (...), by the formula above."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    # (a tensor divisor: by a Python scalar torch multiplies by the reciprocal on a GPU, one ulp off)
+    s = torch.where(amax > 0, amax / torch.full_like(amax, FP8_MAX), torch.ones_like(amax))
+    return (xf / s[..., None]).clamp_(-FP8_MAX, FP8_MAX).to(_E4M3), s
+
+
+def kv_dequantize(plane, scale):
+    """fp32 ``bytes * scale[row]`` of a plane (rows nobody wrote may hold NaN bytes: mask, as the refs do)."""
+    return plane.float() * scale[..., None]
+
+
+def kv_quantize_rows_ref(x, plane, scale):
+    n = x.shape[2]
+    q, s = kv_quantize_ref(x)
+    plane[:, :, :n].copy_(q)
+    scale[:, :, :n].copy_(s)
+
+
+def kv_quantize_rows(x, plane, scale) -> None:
+    """Quantize the rows of ``x`` (B, H, n, d; bf16 / fp16 / fp32, last dim contiguous, any other
+    strides) into rows ``[0, n)`` of the e4m3 ``plane`` (B, H, max_len, d) and its fp32 ``scale``
+    plane (B, H, max_len): what a prefill stores instead of ``copy_``."""
+    if plane.dtype != _E4M3 or scale.dtype != torch.float32 or tuple(scale.shape) != tuple(plane.shape[:-1]):
+        raise ValueError("kv_quantize_rows takes a float8_e4m3fn plane (B, H, max_len, d) and its fp32 scale plane")
+    if x.dim() != 4 or tuple(x.shape[:2]) != tuple(plane.shape[:2]) or x.shape[3] != plane.shape[3] \
+            or x.shape[2] > plane.shape[2]:
+        raise ValueError("kv_quantize_rows: x must be (B, H, n <= max_len, d) for the plane")
+    d = x.shape[-1]
+    if (use_hip(x, plane, scale) and d in _DECODE_D and x.dtype in (torch.bfloat16, torch.float16, torch.float32)
+            and _cache_layout_ok(plane) and _scale_layout_ok(scale)):
+        es = x.element_size()
+        if x.stride(-1) != 1 or x.data_ptr() % 16 or any((x.stride(i) * es) % 16 for i in range(3)):
+            x = x.contiguous()
+        ops().kv_quantize_rows(x, plane, scale)
+        return
+    kv_quantize_rows_ref(x, plane, scale)
 
 
 def decode_attention_ref(q, k_cache, v_cache, kv_len, scale=None):
@@ -76,11 +149,23 @@ def _cache_layout_ok(t: torch.Tensor) -> bool:
             and all((t.stride(i) * es) % 16 == 0 for i in range(3)))
 
 
-def decode_attention(q, k_cache, v_cache, kv_len, scale=None, max_kv_len=None, splits=0):
+def decode_attention(q, k_cache, v_cache, kv_len, scale=None, max_kv_len=None, splits=0, *, k_scale=None, v_scale=None):
     """``max_kv_len``: host-known upper bound of ``kv_len`` (default: the cache's ``max_len``), used
-    only to choose the split count; ``splits``: 0 = choose, n = exactly n key splits."""
+    only to choose the split count; ``splits``: 0 = choose, n = exactly n key splits. ``k_scale`` /
+    ``v_scale``: the scale planes of a ``float8_e4m3fn`` cache."""
     d = q.shape[-1]
     scale = 1.0 / math.sqrt(d) if scale is None else float(scale)
+    if _kv8(k_cache, v_cache, k_scale, v_scale):
+        if (use_hip(q, k_cache, v_cache) and d in _DECODE_D and q.dtype in (torch.bfloat16, torch.float16, torch.float32)
+                and _cache_layout_ok(k_cache) and _cache_layout_ok(v_cache)
+                and _scale_layout_ok(k_scale) and _scale_layout_ok(v_scale)):
+            max_len = k_cache.shape[2]
+            bound = max_len if max_kv_len is None else min(int(max_kv_len), max_len)
+            if kv_len.dtype != torch.int32:
+                kv_len = kv_len.to(torch.int32)
+            return ops().fa_decode_kv8(q, k_cache, v_cache, k_scale, v_scale, kv_len.contiguous(), scale, bound,
+                                       int(splits))
+        return decode_attention_ref(q, kv_dequantize(k_cache, k_scale), kv_dequantize(v_cache, v_scale), kv_len, scale)
     if (use_hip(q, k_cache, v_cache) and d in _DECODE_D and q.dtype in (torch.bfloat16, torch.float16, torch.float32)
             and _cache_layout_ok(k_cache) and _cache_layout_ok(v_cache)):
         max_len = k_cache.shape[2]
@@ -91,8 +176,23 @@ def decode_attention(q, k_cache, v_cache, kv_len, scale=None, max_kv_len=None, s
     return decode_attention_ref(q, k_cache, v_cache, kv_len, scale)
 
 
-def kv_append_rope(qkv, cos, sin, pos, k_cache, v_cache):
+def kv_append_rope_kv8_ref(qkv, cos, sin, pos, k_cache, v_cache, k_scale, v_scale):
+    return kv_append_rope_chunk_kv8_ref(qkv[:, None], cos, sin, pos, k_cache, v_cache, k_scale, v_scale)[:, 0]
+
+
+def kv_append_rope(qkv, cos, sin, pos, k_cache, v_cache, *, k_scale=None, v_scale=None):
     d = k_cache.shape[-1]
+    if _kv8(k_cache, v_cache, k_scale, v_scale):
+        if (use_hip(qkv, k_cache, v_cache) and d in _DECODE_D
+                and qkv.dtype in (torch.bfloat16, torch.float16, torch.float32) and qkv.dim() == 2 and qkv.stride(-1) == 1
+                and qkv.data_ptr() % 16 == 0 and (qkv.stride(0) * qkv.element_size()) % 16 == 0
+                and _cache_layout_ok(k_cache) and _cache_layout_ok(v_cache)
+                and _scale_layout_ok(k_scale) and _scale_layout_ok(v_scale)):
+            if pos.dtype != torch.int32:
+                pos = pos.to(torch.int32)
+            return ops().kv_append_rope_kv8(qkv, cos.float().contiguous(), sin.float().contiguous(), pos.contiguous(),
+                                            k_cache, v_cache, k_scale, v_scale)
+        return kv_append_rope_kv8_ref(qkv, cos, sin, pos, k_cache, v_cache, k_scale, v_scale)
     if (use_hip(qkv, k_cache, v_cache) and d % 8 == 0 and 8 <= d <= 256
             and qkv.dtype in (torch.bfloat16, torch.float16, torch.float32) and qkv.dim() == 2 and qkv.stride(-1) == 1
             and qkv.data_ptr() % 16 == 0 and (qkv.stride(0) * qkv.element_size()) % 16 == 0
@@ -148,11 +248,49 @@ def kv_append_rope_chunk_ref(qkv, cos, sin, pos, k_cache, v_cache):
     return q_rot.transpose(1, 2).contiguous()  # (B, n, H, d)
 
 
-def decode_attention_chunk(q, k_cache, v_cache, kv_len, scale=None, max_kv_len=None, splits=0):
-    """``q`` (B, n, H, d) -> ``o`` (B, n, H, d), ``lse`` (B, n, H). ``max_kv_len`` and ``splits`` as in
-    :func:`decode_attention`."""
+def kv_append_rope_chunk_kv8_ref(qkv, cos, sin, pos, k_cache, v_cache, k_scale, v_scale):
+    """:func:`kv_append_rope_chunk_ref` on the FP8 format: K is rotated in fp32 and rounded once, by
+    the quantizer; q is the sibling's."""
+    B, H, max_len, d = k_cache.shape
+    n = qkv.shape[1]
+    q, k, v = (t.transpose(1, 2) for t in qkv.reshape(B, n, 3, H, d).unbind(2))  # (B, H, n, d)
+    lim = min(max_len, cos.shape[0])
+    slot = pos.to(torch.int64)[:, None] + torch.arange(n, device=qkv.device)[None, :]  # (B, n)
+    ok = (slot >= 0) & (slot < lim)
+    p = slot.clamp(0, lim - 1)
+    q_rot = rope_ref(q, cos, sin, p[:, None, :])
+    k_rot = rope_ref(k.float(), cos.float(), sin.float(), p[:, None, :])
+    r = torch.arange(max_len, device=qkv.device)[None, :]
+    t = r - pos.to(torch.int64)[:, None]  # (B, max_len)
+    take = ((t >= 0) & (t < n) & (r < lim))[:, None, :, None]
+    idx = t.clamp(0, n - 1)[:, None, :, None].expand(B, H, max_len, d)
+    for x, plane, sp in ((k_rot, k_cache, k_scale), (v, v_cache, v_scale)):
+        xq, xs = kv_quantize_ref(x)
+        pb = plane.view(torch.uint8)  # (where / gather have no fp8 kernels)
+        pb.copy_(torch.where(take, xq.view(torch.uint8).gather(2, idx), pb))
+        sp.copy_(torch.where(take[..., 0], xs.gather(2, idx[..., 0]), sp))
+    q_rot = torch.where(ok[:, None, :, None], q_rot, torch.zeros_like(q_rot))
+    return q_rot.transpose(1, 2).contiguous()  # (B, n, H, d)
+
+
+def decode_attention_chunk(q, k_cache, v_cache, kv_len, scale=None, max_kv_len=None, splits=0, *, k_scale=None,
+                           v_scale=None):
+    """``q`` (B, n, H, d) -> ``o`` (B, n, H, d), ``lse`` (B, n, H). ``max_kv_len``, ``splits`` and the
+    scale planes as in :func:`decode_attention`."""
     d = q.shape[-1]
     scale = 1.0 / math.sqrt(d) if scale is None else float(scale)
+    if _kv8(k_cache, v_cache, k_scale, v_scale):
+        if (use_hip(q, k_cache, v_cache) and d in _DECODE_D and q.dtype in (torch.bfloat16, torch.float16, torch.float32)
+                and q.dim() == 4 and q.shape[1] >= 1 and _cache_layout_ok(k_cache) and _cache_layout_ok(v_cache)
+                and _scale_layout_ok(k_scale) and _scale_layout_ok(v_scale)):
+            max_len = k_cache.shape[2]
+            bound = max_len if max_kv_len is None else min(int(max_kv_len), max_len)
+            if kv_len.dtype != torch.int32:
+                kv_len = kv_len.to(torch.int32)
+            return ops().fa_decode_chunk_kv8(q, k_cache, v_cache, k_scale, v_scale, kv_len.contiguous(), scale, bound,
+                                             int(splits))
+        return decode_attention_chunk_ref(q, kv_dequantize(k_cache, k_scale), kv_dequantize(v_cache, v_scale), kv_len,
+                                          scale)
     if (use_hip(q, k_cache, v_cache) and d in _DECODE_D and q.dtype in (torch.bfloat16, torch.float16, torch.float32)
             and q.dim() == 4 and q.shape[1] >= 1 and _cache_layout_ok(k_cache) and _cache_layout_ok(v_cache)):
         max_len = k_cache.shape[2]
@@ -163,9 +301,21 @@ def decode_attention_chunk(q, k_cache, v_cache, kv_len, scale=None, max_kv_len=N
     return decode_attention_chunk_ref(q, k_cache, v_cache, kv_len, scale)
 
 
-def kv_append_rope_chunk(qkv, cos, sin, pos, k_cache, v_cache):
+def kv_append_rope_chunk(qkv, cos, sin, pos, k_cache, v_cache, *, k_scale=None, v_scale=None):
     d = k_cache.shape[-1]
     es = qkv.element_size()
+    if _kv8(k_cache, v_cache, k_scale, v_scale):
+        if (use_hip(qkv, k_cache, v_cache) and d in _DECODE_D
+                and qkv.dtype in (torch.bfloat16, torch.float16, torch.float32) and qkv.dim() == 3 and qkv.shape[1] >= 1
+                and qkv.stride(-1) == 1 and qkv.data_ptr() % 16 == 0
+                and (qkv.stride(0) * es) % 16 == 0 and (qkv.stride(1) * es) % 16 == 0
+                and _cache_layout_ok(k_cache) and _cache_layout_ok(v_cache)
+                and _scale_layout_ok(k_scale) and _scale_layout_ok(v_scale)):
+            if pos.dtype != torch.int32:
+                pos = pos.to(torch.int32)
+            return ops().kv_append_rope_chunk_kv8(qkv, cos.float().contiguous(), sin.float().contiguous(),
+                                                  pos.contiguous(), k_cache, v_cache, k_scale, v_scale)
+        return kv_append_rope_chunk_kv8_ref(qkv, cos, sin, pos, k_cache, v_cache, k_scale, v_scale)
     if (use_hip(qkv, k_cache, v_cache) and d % 8 == 0 and 8 <= d <= 256
             and qkv.dtype in (torch.bfloat16, torch.float16, torch.float32) and qkv.dim() == 3 and qkv.shape[1] >= 1
             and qkv.stride(-1) == 1 and qkv.data_ptr() % 16 == 0

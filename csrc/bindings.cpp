@@ -1596,6 +1596,244 @@ at::Tensor kv_append_rope_chunk(const at::Tensor& qkv, const at::Tensor& cos, co
 int64_t fa_decode_chunk_qt(int64_t n) { return cs336::fa_decode_chunk_qt((int)std::min<int64_t>(n, 1 << 20)); }
 
 // ------------------------------------------------------------------------------------------
+// FP8 KV cache (csrc/flash_attn/fa_decode_kv8.hip, fa_decode_chunk_kv8.hip): k_cache / v_cache are
+// (B, H, max_len, D) e4m3 planes (or their uint8 views), k_scale / v_scale (B, H, max_len) fp32
+// ------------------------------------------------------------------------------------------
+bool is_e4m3(const at::Tensor& t) { return t.scalar_type() == at::kFloat8_e4m3fn || t.scalar_type() == at::kByte; }
+
+cs336::Kv8Scales check_kv8(const at::Tensor& k_cache, const at::Tensor& v_cache, const at::Tensor& k_scale,
+                           const at::Tensor& v_scale) {
+  check_cache(k_cache, "k_cache");
+  check_cache(v_cache, "v_cache");
+  TORCH_CHECK(is_e4m3(k_cache) && is_e4m3(v_cache), "cs336: FP8 caches must be float8_e4m3fn (or its uint8 view)");
+  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "cs336: k_cache / v_cache shape mismatch");
+  const int64_t D = k_cache.size(3);
+  TORCH_CHECK(D == 32 || D == 64 || D == 80 || D == 128, "cs336: FP8 cache head dim must be 32, 64, 80 or 128 (got ", D,
+              ")");
+  const at::Tensor* sc[2] = {&k_scale, &v_scale};
+  for (const at::Tensor* s : sc) {
+    check_cuda(*s, "scale plane");
+    TORCH_CHECK(s->scalar_type() == at::kFloat && s->dim() == 3 && s->size(0) == k_cache.size(0) &&
+                    s->size(1) == k_cache.size(1) && s->size(2) == k_cache.size(2),
+                "cs336: k_scale / v_scale must be fp32 (B, H, max_len) matching the caches");
+    TORCH_CHECK(s->stride(2) == 1 && s->stride(0) >= 0 && s->stride(1) >= 0,
+                "cs336: scale planes need a contiguous last dim");
+    TORCH_CHECK(s->device() == k_cache.device(), "cs336: caches and scale planes must be on one device");
+  }
+  TORCH_CHECK(v_cache.device() == k_cache.device(), "cs336: caches must be on one device");
+  // (the kernels address a key tile's rows with 32-bit offsets)
+  TORCH_CHECK(k_cache.stride(2) < (1 << 22) && v_cache.stride(2) < (1 << 22),
+              "cs336: FP8 cache row stride must be below 2^22 bytes");
+  cs336::Kv8Scales r;
+  r.k = k_scale.data_ptr<float>();
+  r.v = v_scale.data_ptr<float>();
+  r.k_sb = k_scale.stride(0); r.k_sh = k_scale.stride(1);
+  r.v_sb = v_scale.stride(0); r.v_sh = v_scale.stride(1);
+  return r;
+}
+
+std::tuple<at::Tensor, at::Tensor> fa_decode_kv8(const at::Tensor& q, const at::Tensor& k_cache,
+                                                 const at::Tensor& v_cache, const at::Tensor& k_scale,
+                                                 const at::Tensor& v_scale, const at::Tensor& kv_len, double scale,
+                                                 int64_t max_kv_len, int64_t splits) {
+  check_cuda(q, "q");
+  cs336::DecodeKv8Params pp;
+  pp.sc = check_kv8(k_cache, v_cache, k_scale, v_scale);
+  TORCH_CHECK(q.dim() == 3, "cs336: fa_decode_kv8 q must be (B, H, D)");
+  const int64_t B = q.size(0), H = q.size(1), D = q.size(2), max_len = k_cache.size(2);
+  TORCH_CHECK(k_cache.size(0) == B && k_cache.size(1) == H && k_cache.size(3) == D,
+              "cs336: caches must be (B, H, max_len, D) matching q");
+  TORCH_CHECK(k_cache.device() == q.device() && kv_len.device() == q.device(),
+              "cs336: fa_decode_kv8 tensors must be on one device");
+  TORCH_CHECK(kv_len.scalar_type() == at::kInt && kv_len.dim() == 1 && kv_len.size(0) == B && kv_len.is_contiguous(),
+              "cs336: kv_len must be a contiguous int32 (B,) device tensor");
+  TORCH_CHECK(max_kv_len >= 0 && max_kv_len <= max_len, "cs336: max_kv_len must be in [0, max_len]");
+  TORCH_CHECK(splits >= 0 && splits <= 64, "cs336: splits must be in [0, 64] (0 = choose)");
+  TORCH_CHECK(B * H * 64 < ((int64_t)1 << 31), "cs336: fa_decode_kv8 grid too large");
+  const DType t = to_dtype(q);
+  c10::DeviceGuard g(q.device());
+  const at::Tensor qc = q.contiguous();
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(qc.data_ptr()) % 16) == 0, "cs336: q must be 16-byte aligned");
+  at::Tensor o = at::empty({B, H, D}, q.options());
+  at::Tensor lse = at::empty({B, H}, q.options().dtype(at::kFloat));
+  if (B * H == 0) return {o, lse};
+  cs336::DecodeParams& p = pp.base;
+  p.q = qc.data_ptr();
+  p.k = k_cache.data_ptr();
+  p.v = v_cache.data_ptr();
+  p.o = o.data_ptr();
+  p.lse = lse.data_ptr<float>();
+  p.kv_len = kv_len.data_ptr<int>();
+  p.k_sb = k_cache.stride(0); p.k_sh = k_cache.stride(1); p.k_sn = k_cache.stride(2);
+  p.v_sb = v_cache.stride(0); p.v_sh = v_cache.stride(1); p.v_sn = v_cache.stride(2);
+  p.B = (int)B; p.H = (int)H; p.D = (int)D; p.max_len = (int)max_len;
+  p.scale = (float)scale;
+  p.splits = splits > 0 ? (int)splits : cs336::fa_decode_kv8_splits((int)B, (int)H, (int)D, 1, (int)max_kv_len);
+  at::Tensor ws;
+  if (p.splits > 1) {
+    ws = at::empty({(int64_t)p.splits * B * H * (D + 1)}, q.options().dtype(at::kFloat));
+    p.opart = ws.data_ptr<float>();
+    p.lpart = p.opart + (int64_t)p.splits * B * H * D;
+  }
+  cs336::fa_decode_kv8(pp, t, stream());
+  return {o, lse};
+}
+
+std::tuple<at::Tensor, at::Tensor> fa_decode_chunk_kv8(const at::Tensor& q, const at::Tensor& k_cache,
+                                                       const at::Tensor& v_cache, const at::Tensor& k_scale,
+                                                       const at::Tensor& v_scale, const at::Tensor& kv_len,
+                                                       double scale, int64_t max_kv_len, int64_t splits) {
+  check_cuda(q, "q");
+  cs336::DecodeChunkKv8Params pp;
+  pp.sc = check_kv8(k_cache, v_cache, k_scale, v_scale);
+  TORCH_CHECK(q.dim() == 4, "cs336: fa_decode_chunk_kv8 q must be (B, n, H, D)");
+  const int64_t B = q.size(0), n = q.size(1), H = q.size(2), D = q.size(3), max_len = k_cache.size(2);
+  TORCH_CHECK(n >= 1, "cs336: fa_decode_chunk_kv8 needs at least one query row");
+  TORCH_CHECK(k_cache.size(0) == B && k_cache.size(1) == H && k_cache.size(3) == D,
+              "cs336: caches must be (B, H, max_len, D) matching q");
+  TORCH_CHECK(k_cache.device() == q.device() && kv_len.device() == q.device(),
+              "cs336: fa_decode_chunk_kv8 tensors must be on one device");
+  TORCH_CHECK(kv_len.scalar_type() == at::kInt && kv_len.dim() == 1 && kv_len.size(0) == B && kv_len.is_contiguous(),
+              "cs336: kv_len must be a contiguous int32 (B,) device tensor");
+  TORCH_CHECK(max_kv_len >= 0 && max_kv_len <= max_len, "cs336: max_kv_len must be in [0, max_len]");
+  TORCH_CHECK(splits >= 0 && splits <= 64, "cs336: splits must be in [0, 64] (0 = choose)");
+  TORCH_CHECK(n < ((int64_t)1 << 20), "cs336: fa_decode_chunk_kv8 n too large");
+  const int64_t QT = cs336::fa_decode_kv8_chunk_qt((int)n), qtiles = (n + QT - 1) / QT;
+  TORCH_CHECK(B * H < ((int64_t)1 << 31) && B * H * qtiles < ((int64_t)1 << 31) / 64 && B * n * H < ((int64_t)1 << 31),
+              "cs336: fa_decode_chunk_kv8 grid too large");
+  const DType t = to_dtype(q);
+  c10::DeviceGuard g(q.device());
+  const at::Tensor qc = q.contiguous();
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(qc.data_ptr()) % 16) == 0, "cs336: q must be 16-byte aligned");
+  at::Tensor o = at::empty({B, n, H, D}, q.options());
+  at::Tensor lse = at::empty({B, n, H}, q.options().dtype(at::kFloat));
+  if (B * H == 0) return {o, lse};
+  cs336::DecodeChunkParams& p = pp.base;
+  p.q = qc.data_ptr();
+  p.k = k_cache.data_ptr();
+  p.v = v_cache.data_ptr();
+  p.o = o.data_ptr();
+  p.lse = lse.data_ptr<float>();
+  p.kv_len = kv_len.data_ptr<int>();
+  p.k_sb = k_cache.stride(0); p.k_sh = k_cache.stride(1); p.k_sn = k_cache.stride(2);
+  p.v_sb = v_cache.stride(0); p.v_sh = v_cache.stride(1); p.v_sn = v_cache.stride(2);
+  p.B = (int)B; p.n = (int)n; p.H = (int)H; p.D = (int)D; p.max_len = (int)max_len;
+  p.scale = (float)scale;
+  p.splits = splits > 0 ? (int)splits : cs336::fa_decode_kv8_splits((int)B, (int)H, (int)D, (int)n, (int)max_kv_len);
+  at::Tensor ws;
+  if (p.splits > 1) {
+    ws = at::empty({(int64_t)p.splits * B * n * H * (D + 1)}, q.options().dtype(at::kFloat));
+    p.opart = ws.data_ptr<float>();
+    p.lpart = p.opart + (int64_t)p.splits * B * n * H * D;
+  }
+  cs336::fa_decode_chunk_kv8(pp, t, stream());
+  return {o, lse};
+}
+
+// qkv (B, 3*H*D) -> q_out (B, H, D), or (B, n, 3*H*D) -> (B, n, H, D)
+at::Tensor append_kv8(const at::Tensor& qkv, bool chunk, const at::Tensor& cos, const at::Tensor& sin,
+                      const at::Tensor& pos, at::Tensor& k_cache, at::Tensor& v_cache, at::Tensor& k_scale,
+                      at::Tensor& v_scale) {
+  check_cuda(qkv, "qkv");
+  cs336::AppendKv8Params pp;
+  pp.sc = check_kv8(k_cache, v_cache, k_scale, v_scale);
+  const int64_t B = k_cache.size(0), H = k_cache.size(1), max_len = k_cache.size(2), D = k_cache.size(3);
+  TORCH_CHECK(qkv.dim() == (chunk ? 3 : 2) && qkv.stride(-1) == 1 && qkv.size(0) == B && qkv.size(-1) == 3 * H * D,
+              "cs336: qkv must be (B, [n,] 3*H*D) with a contiguous last dim for (B, H, max_len, D) caches");
+  const int64_t n = chunk ? qkv.size(1) : 1;
+  const int64_t es = qkv.element_size();
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16) == 0 && (qkv.stride(0) * es) % 16 == 0 &&
+                  qkv.stride(0) >= 0 && (!chunk || ((qkv.stride(1) * es) % 16 == 0 && qkv.stride(1) >= 0)),
+              "cs336: qkv rows must be 16-byte aligned");
+  TORCH_CHECK(cos.is_cuda() && sin.is_cuda() && cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat &&
+                  cos.dim() == 2 && cos.is_contiguous() && sin.is_contiguous() && cos.sizes() == sin.sizes() &&
+                  cos.size(1) * 2 == D,
+              "cs336: rope cache must be contiguous fp32 (ctx, D/2)");
+  TORCH_CHECK(pos.scalar_type() == at::kInt && pos.dim() == 1 && pos.size(0) == B && pos.is_contiguous(),
+              "cs336: pos must be a contiguous int32 (B,) device tensor");
+  TORCH_CHECK(pos.device() == qkv.device() && cos.device() == qkv.device() && sin.device() == qkv.device() &&
+                  k_cache.device() == qkv.device(),
+              "cs336: kv_append_rope_kv8 tensors must be on one device");
+  TORCH_CHECK(n < ((int64_t)1 << 31) && B * n < ((int64_t)1 << 31) / (3 * H > 0 ? 3 * H : 1) &&
+                  cos.size(0) < ((int64_t)1 << 31),
+              "cs336: kv_append_rope_kv8 too large for 32-bit indexing");
+  const DType t = to_dtype(qkv);
+  c10::DeviceGuard g(qkv.device());
+  at::Tensor q_out = chunk ? at::empty({B, n, H, D}, qkv.options()) : at::empty({B, H, D}, qkv.options());
+  if (B * H * n == 0) return q_out;
+  cs336::AppendChunkParams& p = pp.base;
+  p.qkv = qkv.data_ptr();
+  p.qkv_sb = qkv.stride(0);
+  p.qkv_sn = chunk ? qkv.stride(1) : 0;
+  p.cos = cos.data_ptr<float>();
+  p.sin = sin.data_ptr<float>();
+  p.pos = pos.data_ptr<int>();
+  p.q_out = q_out.data_ptr();
+  p.k = k_cache.data_ptr();
+  p.v = v_cache.data_ptr();
+  p.k_sb = k_cache.stride(0); p.k_sh = k_cache.stride(1); p.k_sn = k_cache.stride(2);
+  p.v_sb = v_cache.stride(0); p.v_sh = v_cache.stride(1); p.v_sn = v_cache.stride(2);
+  p.B = (int)B; p.n = (int)n; p.H = (int)H; p.D = (int)D; p.max_len = (int)max_len; p.ctx = (int)cos.size(0);
+  cs336::kv_append_rope_kv8(pp, t, stream());
+  return q_out;
+}
+
+at::Tensor kv_append_rope_kv8(const at::Tensor& qkv, const at::Tensor& cos, const at::Tensor& sin,
+                              const at::Tensor& pos, at::Tensor& k_cache, at::Tensor& v_cache, at::Tensor& k_scale,
+                              at::Tensor& v_scale) {
+  return append_kv8(qkv, false, cos, sin, pos, k_cache, v_cache, k_scale, v_scale);
+}
+
+at::Tensor kv_append_rope_chunk_kv8(const at::Tensor& qkv, const at::Tensor& cos, const at::Tensor& sin,
+                                    const at::Tensor& pos, at::Tensor& k_cache, at::Tensor& v_cache,
+                                    at::Tensor& k_scale, at::Tensor& v_scale) {
+  return append_kv8(qkv, true, cos, sin, pos, k_cache, v_cache, k_scale, v_scale);
+}
+
+// x (B, H, n, D) bf16 / fp16 / fp32, any batch / head / row strides -> rows [0, n) of plane and scale
+void kv_quantize_rows(const at::Tensor& x, at::Tensor& plane, at::Tensor& scale) {
+  check_cuda(x, "x");
+  check_cache(plane, "plane");
+  check_cuda(scale, "scale");
+  TORCH_CHECK(is_e4m3(plane), "cs336: kv_quantize_rows plane must be float8_e4m3fn (or its uint8 view)");
+  TORCH_CHECK(x.dim() == 4 && x.stride(3) == 1, "cs336: kv_quantize_rows x must be (B, H, n, D) with a contiguous last dim");
+  const int64_t B = x.size(0), H = x.size(1), n = x.size(2), D = x.size(3);
+  TORCH_CHECK(D == 32 || D == 64 || D == 80 || D == 128, "cs336: kv_quantize_rows head dim must be 32, 64, 80 or 128");
+  TORCH_CHECK(plane.size(0) == B && plane.size(1) == H && plane.size(3) == D && n <= plane.size(2),
+              "cs336: plane must be (B, H, max_len >= n, D)");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.dim() == 3 && scale.size(0) == B && scale.size(1) == H &&
+                  scale.size(2) == plane.size(2) && scale.stride(2) == 1 && scale.stride(0) >= 0 && scale.stride(1) >= 0,
+              "cs336: scale must be fp32 (B, H, max_len) with a contiguous last dim");
+  const int64_t es = x.element_size();
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(x.data_ptr()) % 16) == 0 && (x.stride(0) * es) % 16 == 0 &&
+                  (x.stride(1) * es) % 16 == 0 && (x.stride(2) * es) % 16 == 0 && x.stride(0) >= 0 && x.stride(1) >= 0 &&
+                  x.stride(2) >= 0,
+              "cs336: kv_quantize_rows x rows must be 16-byte aligned");
+  TORCH_CHECK(plane.device() == x.device() && scale.device() == x.device(),
+              "cs336: kv_quantize_rows tensors must be on one device");
+  const DType t = to_dtype(x);
+  if (B * H * n == 0) return;
+  c10::DeviceGuard g(x.device());
+  cs336::QuantizeRowsParams p;
+  p.x = x.data_ptr();
+  p.x_sb = x.stride(0); p.x_sh = x.stride(1); p.x_sn = x.stride(2);
+  p.out = plane.data_ptr();
+  p.o_sb = plane.stride(0); p.o_sh = plane.stride(1); p.o_sn = plane.stride(2);
+  p.scale = scale.data_ptr<float>();
+  p.s_sb = scale.stride(0); p.s_sh = scale.stride(1);
+  p.B = (int)B; p.H = (int)H; p.n = (int)n; p.D = (int)D;
+  cs336::kv_quantize_rows(p, t, stream());
+}
+
+// key tile and split count of the FP8-cache kernels for an n-query step (tests and benchmarks)
+int64_t fa_decode_kv8_key_tile(int64_t D, int64_t n) {
+  return cs336::fa_decode_kv8_key_tile((int)D, (int)std::min<int64_t>(n, 1 << 20));
+}
+int64_t fa_decode_kv8_splits(int64_t B, int64_t H, int64_t D, int64_t n, int64_t max_kv_len) {
+  return cs336::fa_decode_kv8_splits((int)B, (int)H, (int)D, (int)std::min<int64_t>(n, 1 << 20), (int)max_kv_len);
+}
+
+// ------------------------------------------------------------------------------------------
 // Skinny-M GEMM for decode (csrc/gemm/gemm_skinny.hip), M <= 16, x / out bf16 or fp16:
 //   gemm_skinny:    out[M,N] = x[M,K] · w[N,K]ᵀ, w of x's dtype
 //   gemm_skinny_w8: out[M,N] = (x[M,K] · wq[N,K]ᵀ) * scale[N], wq e4m3 (or its uint8 view)
@@ -1685,6 +1923,21 @@ TORCH_LIBRARY(cs336, m) {
       "-> Tensor");
   m.def("fa_decode_chunk_qt(int n) -> int", &fa_decode_chunk_qt);
   m.def(
+      "fa_decode_kv8(Tensor q, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, Tensor kv_len, "
+      "float scale, int max_kv_len, int splits=0) -> (Tensor o, Tensor lse)");
+  m.def(
+      "fa_decode_chunk_kv8(Tensor q, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, Tensor kv_len, "
+      "float scale, int max_kv_len, int splits=0) -> (Tensor, Tensor)");
+  m.def(
+      "kv_append_rope_kv8(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor(a!) k_cache, Tensor(b!) v_cache, "
+      "Tensor(c!) k_scale, Tensor(d!) v_scale) -> Tensor");
+  m.def(
+      "kv_append_rope_chunk_kv8(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor(a!) k_cache, "
+      "Tensor(b!) v_cache, Tensor(c!) k_scale, Tensor(d!) v_scale) -> Tensor");
+  m.def("kv_quantize_rows(Tensor x, Tensor(a!) plane, Tensor(b!) scale) -> ()");
+  m.def("fa_decode_kv8_key_tile(int D, int n) -> int", &fa_decode_kv8_key_tile);
+  m.def("fa_decode_kv8_splits(int B, int H, int D, int n, int max_kv_len) -> int", &fa_decode_kv8_splits);
+  m.def(
       "fa_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale, Tensor? rope_cos=None, Tensor? rope_sin=None, "
       "Tensor? rope_pos=None) -> (Tensor, Tensor)");
   m.def(
@@ -1751,6 +2004,11 @@ TORCH_LIBRARY_IMPL(cs336, CUDA, m) {
   m.impl("kv_append_rope", &kv_append_rope);
   m.impl("fa_decode_chunk", &fa_decode_chunk);
   m.impl("kv_append_rope_chunk", &kv_append_rope_chunk);
+  m.impl("fa_decode_kv8", &fa_decode_kv8);
+  m.impl("fa_decode_chunk_kv8", &fa_decode_chunk_kv8);
+  m.impl("kv_append_rope_kv8", &kv_append_rope_kv8);
+  m.impl("kv_append_rope_chunk_kv8", &kv_append_rope_chunk_kv8);
+  m.impl("kv_quantize_rows", &kv_quantize_rows);
   m.impl("fa_fwd", &fa_fwd);
   m.impl("fa_fwd_ot", &fa_fwd_ot);
   m.impl("fa_bwd", &fa_bwd);

@@ -263,11 +263,15 @@ __global__ __launch_bounds__(256) void kv_append_rope_kernel(const AppendParams 
 }
 
 template <typename T, int D>
+void launch_merge(const DecodeParams& p, hipStream_t s) {
+  hipLaunchKernelGGL((fa_decode_merge_kernel<T, D>), dim3((unsigned)(p.B * p.H)), dim3(128), 0, s, p);
+}
+
+template <typename T, int D>
 void launch_decode(const DecodeParams& p, hipStream_t s) {
   const dim3 grid((unsigned)((int64_t)p.B * p.H * p.splits));
   hipLaunchKernelGGL((fa_decode_kernel<T, D>), grid, dim3(kDecodeThreads), 0, s, p);
-  if (p.splits > 1)
-    hipLaunchKernelGGL((fa_decode_merge_kernel<T, D>), dim3((unsigned)(p.B * p.H)), dim3(128), 0, s, p);
+  if (p.splits > 1) launch_merge<T, D>(p, s);
 }
 
 template <typename T>
@@ -278,6 +282,17 @@ void launch_decode_d(const DecodeParams& p, hipStream_t s) {
     case 80: launch_decode<T, 80>(p, s); break;
     case 128: launch_decode<T, 128>(p, s); break;
     default: abort();  // the binding checks the head dim
+  }
+}
+
+template <typename T>
+void launch_merge_d(const DecodeParams& p, hipStream_t s) {
+  switch (p.D) {
+    case 32: launch_merge<T, 32>(p, s); break;
+    case 64: launch_merge<T, 64>(p, s); break;
+    case 80: launch_merge<T, 80>(p, s); break;
+    case 128: launch_merge<T, 128>(p, s); break;
+    default: abort();
   }
 }
 
@@ -309,6 +324,15 @@ void fa_decode(const DecodeParams& p, DType t, hipStream_t s) {
     case DType::F32: launch_decode_d<float>(p, s); break;
     case DType::BF16: launch_decode_d<BF16>(p, s); break;
     case DType::F16: launch_decode_d<F16>(p, s); break;
+  }
+}
+
+void fa_decode_merge(const DecodeParams& p, DType t, hipStream_t s) {
+  if (p.B <= 0 || p.H <= 0) return;
+  switch (t) {
+    case DType::F32: launch_merge_d<float>(p, s); break;
+    case DType::BF16: launch_merge_d<BF16>(p, s); break;
+    case DType::F16: launch_merge_d<F16>(p, s); break;
   }
 }
 

@@ -319,15 +319,30 @@ void launch_chunk_qt(const DecodeChunkParams& p, hipStream_t s) {
 }
 
 template <typename T, int D>
+void launch_chunk_merge(const DecodeChunkParams& p, hipStream_t s) {
+  hipLaunchKernelGGL((fa_decode_chunk_merge_kernel<T, D>), dim3((unsigned)((int64_t)p.B * p.n * p.H)), dim3(128), 0, s,
+                     p);
+}
+
+template <typename T>
+void launch_chunk_merge_d(const DecodeChunkParams& p, hipStream_t s) {
+  switch (p.D) {
+    case 32: launch_chunk_merge<T, 32>(p, s); break;
+    case 64: launch_chunk_merge<T, 64>(p, s); break;
+    case 80: launch_chunk_merge<T, 80>(p, s); break;
+    case 128: launch_chunk_merge<T, 128>(p, s); break;
+    default: abort();
+  }
+}
+
+template <typename T, int D>
 void launch_chunk(const DecodeChunkParams& p, hipStream_t s) {
   switch (fa_decode_chunk_qt(p.n)) {
     case 1: launch_chunk_qt<T, D, 1>(p, s); break;
     case 4: launch_chunk_qt<T, D, 4>(p, s); break;
     default: launch_chunk_qt<T, D, kDecodeChunkQT>(p, s); break;
   }
-  if (p.splits > 1)
-    hipLaunchKernelGGL((fa_decode_chunk_merge_kernel<T, D>), dim3((unsigned)((int64_t)p.B * p.n * p.H)), dim3(128), 0,
-                       s, p);
+  if (p.splits > 1) launch_chunk_merge<T, D>(p, s);
 }
 
 template <typename T>
@@ -351,6 +366,15 @@ void fa_decode_chunk(const DecodeChunkParams& p, DType t, hipStream_t s) {
     case DType::F32: launch_chunk_d<float>(p, s); break;
     case DType::BF16: launch_chunk_d<BF16>(p, s); break;
     case DType::F16: launch_chunk_d<F16>(p, s); break;
+  }
+}
+
+void fa_decode_chunk_merge(const DecodeChunkParams& p, DType t, hipStream_t s) {
+  if (p.B <= 0 || p.H <= 0 || p.n <= 0) return;
+  switch (t) {
+    case DType::F32: launch_chunk_merge_d<float>(p, s); break;
+    case DType::BF16: launch_chunk_merge_d<BF16>(p, s); break;
+    case DType::F16: launch_chunk_merge_d<F16>(p, s); break;
   }
 }
 

@@ -304,6 +304,61 @@ struct AppendChunkParams {
 };
 void kv_append_rope_chunk(const AppendChunkParams& p, DType t, hipStream_t s);
 
+// the second launch of fa_decode / fa_decode_chunk at splits > 1 on its own: o / lse from the fp32
+// partials opart / lpart (reads o, lse, opart, lpart, B, (n,) H, D, splits of p; t is o's type). The
+// partials do not depend on the cache format, so the FP8-cache kernels below merge with these.
+void fa_decode_merge(const DecodeParams& p, DType t, hipStream_t s);
+void fa_decode_chunk_merge(const DecodeChunkParams& p, DType t, hipStream_t s);
+
+// ---- FP8 KV cache (csrc/flash_attn/fa_decode_kv8.hip, fa_decode_chunk_kv8.hip) ----
+// A cached row is D OCP e4m3 bytes and one fp32 scale, row = bytes * scale: k / v of the structs are
+// (B, H, max_len, D) byte planes (strides in bytes, rows 16-B aligned, row stride below 2^22) and k_scale / v_scale
+// (B, H, max_len) fp32 planes with a contiguous last dim. A row is quantized when it is written:
+// scale = amax > 0 ? amax / 448 : 1 over its D fp32 values, bytes = RNE(clamp(x / scale, +-448)).
+// D in {32, 64, 80, 128}; q / o / qkv bf16, fp16 or fp32 (DType).
+struct Kv8Scales {
+  float* k;  // (the attention kernels only read them)
+  float* v;
+  int64_t k_sb, k_sh;  // batch / head strides (elements)
+  int64_t v_sb, v_sh;
+};
+// fa_decode / fa_decode_chunk on the FP8 format (base.k / base.v the byte planes)
+struct DecodeKv8Params {
+  DecodeParams base;
+  Kv8Scales sc;
+};
+struct DecodeChunkKv8Params {
+  DecodeChunkParams base;
+  Kv8Scales sc;
+};
+// the query tile of an n-query step (1 for n == 1, fa_decode_kv8's kernel; else 4, with ceil(n / 4)
+// query tiles), its keys per tile, and the split count the host picks with them (fa_decode_splits' rule)
+int fa_decode_kv8_chunk_qt(int n);
+int fa_decode_kv8_key_tile(int D, int n);
+int fa_decode_kv8_splits(int B, int H, int D, int n, int max_kv_len);
+void fa_decode_kv8(const DecodeKv8Params& p, DType t, hipStream_t s);
+void fa_decode_chunk_kv8(const DecodeChunkKv8Params& p, DType t, hipStream_t s);
+// kv_append_rope / kv_append_rope_chunk on the FP8 format: rotated q -> q_out in qkv's type; the fp32
+// rotated k and the plain v row are quantized (one rounding) into row pos[b] + i of the four planes.
+// One kernel serves both (the single append is base.n == 1, base.qkv_sn unused).
+struct AppendKv8Params {
+  AppendChunkParams base;
+  Kv8Scales sc;
+};
+void kv_append_rope_kv8(const AppendKv8Params& p, DType t, hipStream_t s);
+// the prefill's store: rows x (B, H, n, D; strides in elements, last dim contiguous, 16-B aligned
+// chunks of 8) -> rows [0, n) of a byte plane `out` and its scale plane
+struct QuantizeRowsParams {
+  const void* x;
+  int64_t x_sb, x_sh, x_sn;
+  void* out;
+  int64_t o_sb, o_sh, o_sn;
+  float* scale;
+  int64_t s_sb, s_sh;
+  int B, H, n, D;
+};
+void kv_quantize_rows(const QuantizeRowsParams& p, DType t, hipStream_t s);
+
 // ---- skinny-M GEMM for decode, 16-bit or FP8 weights (csrc/gemm/gemm_skinny.hip) ----
 // W16:  out[M,N] = x[M,K] · w[N,K]ᵀ, w of x's type.
 // E4M3: out[M,N] = round(fp32(x[M,K] · w[N,K]ᵀ) * scale[N]), w OCP e4m3 bytes, scale fp32 per W row.
