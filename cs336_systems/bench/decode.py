@@ -47,6 +47,16 @@ end-to-end point context 4096, B 8, prompt 2048 + 512, where the cache is the la
 
     python -m cs336_systems.bench.decode --kv-fp8 --chunk --no-e2e --json profiles/decode_kv8_chunk.json
     python -m cs336_systems.bench.decode --kv-fp8 --no-sweep --arms graph graph+kv8 graph+fp8+kv8 --json profiles/decode_kv8.json
+
+Fused sampler (``--sample``; ``csrc/ops/sample.hip``): ``ops.sample_logits`` at B 1 / 8 / 64 x V 10000 /
+50257 x top_k 1 / 50 / none on bf16 ``logits[:, -1]`` rows, against the eager pipeline of ``generate`` it
+replaces (``float() / temperature``, ``topk``, ``masked_fill``, ``softmax``, ``multinomial``) in the same run:
+median and q20-q80 over the same 50 flushed calls, faster / slower only beyond the spread of both sides.
+The arms ``graph+sample`` and ``graph+fp8+sample`` are ``generate(..., graph=True, sample_on_device=True)``:
+ms per token beside the ``graph`` arm of the same run; with ``--sample`` every arm is timed three times
+(all runs are kept, the median is reported).
+
+    python -m cs336_systems.bench.decode --sample --no-kernel --arms graph graph+sample graph+fp8 graph+fp8+sample --json profiles/decode_sample.json
 """
 
 from __future__ import annotations
@@ -276,10 +286,39 @@ def skinny_row(model_size: str, name: str, M: int, N: int, K: int, warmup: int =
     return row
 
 
+SAMPLE_B, SAMPLE_V, SAMPLE_K = (1, 8, 64), (10000, 50257), (1, 50, None)
+
+
+def sample_row(B: int, V: int, top_k, warmup: int = 10, rep: int = 50) -> dict:
+    """The fused sampler against the eager sampling of ``generate`` on the same logits."""
+    torch.manual_seed(0)
+    x = (torch.randn(B, 1, V, device="cuda") * 4).to(torch.bfloat16)[:, -1]
+    u = torch.rand(B, device="cuda")
+    temperature = 0.8
+
+    def eager():
+        logits = x.float() / temperature
+        if top_k:
+            vals, _ = torch.topk(logits, min(top_k, V))
+            logits = logits.masked_fill(logits < vals[:, -1:], float("-inf"))
+        return torch.multinomial(torch.softmax(logits, dim=-1), 1)
+
+    row = dict(B=B, V=V, top_k=top_k, dtype="bf16", logits_kbytes=B * V * 2 / 1024)
+    for key, fn in (("fused", lambda: ops.sample_logits(x, u, temperature, top_k)), ("eager", eager)):
+        med, lo, hi = do_bench(fn, warmup=warmup, rep=rep)
+        row[f"{key}_us"], row[f"{key}_us_q20"], row[f"{key}_us_q80"] = med * 1e3, lo * 1e3, hi * 1e3
+    row["fused_vs_eager"] = row["fused_us"] / row["eager_us"]  # below 1: the fused kernel is faster
+    row["verdict"] = ("faster" if row["fused_us_q80"] < row["eager_us_q20"] else
+                      "slower" if row["fused_us_q20"] > row["eager_us_q80"] else "same")
+    return row
+
+
 ARMS = {"cached": dict(use_cache=True), "uncached": dict(use_cache=False), "graph": dict(use_cache=True, graph=True),
         "graph+fp8": dict(use_cache=True, graph=True),  # (+ weights=Fp8DecodeWeights(model), built per model)
         "graph+kv8": dict(use_cache=True, graph=True, kv_fp8=True),
-        "graph+fp8+kv8": dict(use_cache=True, graph=True, kv_fp8=True)}  # (+ weights)
+        "graph+fp8+kv8": dict(use_cache=True, graph=True, kv_fp8=True),  # (+ weights)
+        "graph+sample": dict(use_cache=True, graph=True, sample_on_device=True),
+        "graph+fp8+sample": dict(use_cache=True, graph=True, sample_on_device=True)}  # (+ weights)
 ARM_KEYS = {"graph": "cached_graph", "graph+fp8": "cached_graph_fp8", "graph+kv8": "cached_graph_kv8",
             "graph+fp8+kv8": "cached_graph_fp8_kv8"}
 
@@ -308,7 +347,8 @@ def replay_ms(model, x: torch.Tensor, weights=None, rep: int = 50, kv_fp8: bool 
     return ts[len(ts) // 2], ts[len(ts) // 5], ts[len(ts) * 4 // 5]
 
 
-def e2e_row(model_size: str, ctx: int, B: int, prompt: int, new: int, arms=("cached", "uncached", "graph")) -> dict:
+def e2e_row(model_size: str, ctx: int, B: int, prompt: int, new: int, arms=("cached", "uncached", "graph"),
+            runs: int = 1) -> dict:
     from ..models import build_model
 
     torch.manual_seed(0)
@@ -318,20 +358,25 @@ def e2e_row(model_size: str, ctx: int, B: int, prompt: int, new: int, arms=("cac
     qw = None
     for arm in arms:
         kw = dict(ARMS[arm])
-        if arm in ("graph+fp8", "graph+fp8+kv8"):
+        if arm in ("graph+fp8", "graph+fp8+kv8", "graph+fp8+sample"):
             from ..models import Fp8DecodeWeights
 
             qw = qw or Fp8DecodeWeights(model)
             kw["weights"] = qw
             row["fp8_weight_mbytes"] = qw.nbytes / 2**20
         model.generate(x, 4, top_k=1, **kw)  # warm-up: GEMM selection, allocator
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = model.generate(x, new, top_k=1, **kw)  # (the graph arm's time includes its capture)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        assert out.shape == (B, new)
-        name = ARM_KEYS.get(arm, arm)
+        dts = []
+        for _ in range(runs):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = model.generate(x, new, top_k=1, **kw)  # (the graph arm's time includes its capture)
+            torch.cuda.synchronize()
+            dts.append(time.perf_counter() - t0)
+            assert out.shape == (B, new)
+        dt = sorted(dts)[len(dts) // 2]
+        name = ARM_KEYS.get(arm, arm.replace("graph", "cached_graph").replace("+", "_"))
+        if runs > 1:
+            row[f"{name}_ms_per_step_runs"] = [t / new * 1e3 for t in dts]
         row[f"{name}_s"] = dt
         row[f"{name}_tok_s"] = B * new / dt
         row[f"{name}_ms_per_step"] = dt / new * 1e3
@@ -353,6 +398,13 @@ def e2e_row(model_size: str, ctx: int, B: int, prompt: int, new: int, arms=("cac
     if "cached_graph_s" in row and "cached_graph_fp8_s" in row:
         row["fp8_speedup_vs_graph"] = row["cached_graph_s"] / row["cached_graph_fp8_s"]
         row["fp8_replay_vs_graph"] = row["cached_graph_fp8_replay_ms"] / row["cached_graph_replay_ms"]
+    for name, base in (("cached_graph_sample", "cached_graph"), ("cached_graph_fp8_sample", "cached_graph_fp8")):
+        if f"{name}_s" in row and f"{base}_s" in row:
+            row[f"{name}_vs_{base[7:]}"] = row[f"{name}_s"] / row[f"{base}_s"]  # below 1: sampling in the graph is faster
+            row[f"{name}_saves_ms_per_step"] = row[f"{base}_ms_per_step"] - row[f"{name}_ms_per_step"]
+            if runs > 1:  # faster / slower only when every run of one side beats every run of the other
+                a, b = row[f"{name}_ms_per_step_runs"], row[f"{base}_ms_per_step_runs"]
+                row[f"{name}_verdict"] = "faster" if max(a) < min(b) else "slower" if min(a) > max(b) else "same"
     for name in ("cached_graph_kv8", "cached_graph_fp8_kv8"):
         if "cached_graph_s" in row and f"{name}_s" in row:
             row[f"{name}_speedup_vs_graph"] = row["cached_graph_s"] / row[f"{name}_s"]
@@ -380,6 +432,9 @@ def main(argv=None):
     ap.add_argument("--kv-fp8", action="store_true",
                     help="add the FP8 KV cache kernels to every kernel / chunk row, and the end-to-end point "
                          "context 4096, B 8, prompt 2048 + 512")
+    ap.add_argument("--sample", action="store_true",
+                    help="the fused sampler table (sample_logits against the eager sampling of generate), and three "
+                         "timed runs per end-to-end arm")
     ap.add_argument("--chunk", action="store_true",
                     help="the multi-token tables: decode_attention_chunk rows instead of the single-token sweep, and "
                          "(with --arms verify) the replayed n-token step; no generate arms")
@@ -432,12 +487,20 @@ def main(argv=None):
                     r = skinny_row(size, name, M, N, K, rep=a.rep, fp8=a.fp8)
                     out["skinny"].append(r)
                     print(json.dumps(r), flush=True)
+    if a.sample:
+        out["sample"] = []
+        for B in SAMPLE_B:
+            for V in SAMPLE_V:
+                for k in SAMPLE_K:
+                    r = sample_row(B, V, k, rep=a.rep)
+                    out["sample"].append(r)
+                    print(json.dumps(r), flush=True)
     if not a.no_e2e:
         points = [(512, 1, 128, 384), (512, 8, 128, 384), (4096, 1, 2048, 512)]
         if a.kv_fp8:
             points.append((4096, 8, 2048, 512))  # the cache is the larger stream of a step
         for ctx, B, prompt, new in points:
-            r = e2e_row(a.model, ctx, B, prompt, new, arms=a.arms)
+            r = e2e_row(a.model, ctx, B, prompt, new, arms=a.arms, runs=3 if a.sample else 1)
             out["e2e"].append(r)
             print(json.dumps(r), flush=True)
     if a.json:

@@ -1,5 +1,5 @@
 from .configs import DEFAULT_THETA, DEFAULT_VOCAB, MODEL_CONFIGS, get_model_config, param_count, train_flops_per_token
-from .decode_graph import DecodeGraph
+from .decode_graph import DecodeGraph, Sampler
 from .kv_cache import KVCache
 from .quantized import Fp8DecodeWeights
 from .speculative import speculative_generate
@@ -38,6 +38,7 @@ __all__ = [
     "Linear",
     "RMSNorm",
     "RotaryEmbedding",
+    "Sampler",
     "SwiGLU",
     "TransformerBlock",
     "MODEL_CONFIGS",

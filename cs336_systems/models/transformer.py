@@ -714,6 +714,9 @@ class BasicsTransformerLM(nn.Module):
         draft_tokens: int = 4,
         weights=None,
         kv_fp8: bool = False,
+        sample_on_device: bool = False,
+        generator=None,
+        sync_every: int = 16,
     ) -> torch.Tensor:
         """Autoregressive sampling (``model.py:255-310``) with a working top-k filter (the
         reference's ``masked_fill`` is not in place and its threshold broadcast is wrong for B>1).
@@ -742,11 +745,29 @@ class BasicsTransformerLM(nn.Module):
         ``draft=<model>``: greedy speculative decoding (``models/speculative.py``): the draft proposes
         ``draft_tokens`` tokens per round and this model verifies them in one chunk step; the output
         is exactly the greedy one. Needs ``use_cache=True``, ``top_k == 1`` and a bool ``graph``;
-        sampling from a draft is not supported."""
+        sampling from a draft is not supported.
+
+        ``sample_on_device=True`` (with ``use_cache=True``): every token is sampled by the fused sampler
+        (``ops.sample_logits``, the rule of ``ops/sample.py``) from ONE table ``u = torch.rand(max_new_tokens,
+        B, generator=generator)`` drawn up front, token ``s`` from row ``u[s]`` whichever path computes its
+        logits: the prefill, the cached steps (with ``graph=`` inside the graph, ``DecodeGraph(sampler=)``:
+        the host issues one replay per token and reads nothing back) and the sliding-window tail. The
+        tokens are a function of the weights, the prompt and the table, whatever the batch. With
+        ``eos_token_id`` the host polls every ``sync_every`` tokens and stops once every row has ended. At
+        B == 1 the result is cut before the first end token, as without this switch; at B > 1 a row that has
+        ended keeps emitting ``eos_token_id`` and the result is rectangular, up to and including the column
+        in which the last row ended. ``draft=`` raises: speculation stays greedy."""
         from .decode_graph import DecodeGraph
 
         if kv_fp8 and not use_cache:
             raise ValueError("generate(kv_fp8=True) needs use_cache=True")
+        if sample_on_device:
+            if draft is not None:
+                raise ValueError("generate(sample_on_device=True) does not take draft=: speculation is greedy")
+            if not use_cache:
+                raise ValueError("generate(sample_on_device=True) needs use_cache=True")
+            return self._generate_on_device(x, max_new_tokens, temperature, top_k, eos_token_id, graph, weights, kv_fp8,
+                                            generator, sync_every)
         if draft is not None:
             from .speculative import speculative_generate
 
@@ -812,6 +833,100 @@ class BasicsTransformerLM(nn.Module):
                 break
             x = torch.cat((x, nxt), dim=-1)
         return x[:, orig:]
+
+    def _generate_on_device(self, x, max_new_tokens, temperature, top_k, eos_token_id, graph, weights, kv_fp8,
+                            generator, sync_every) -> torch.Tensor:
+        """``generate(sample_on_device=True)``: see there."""
+        from .decode_graph import DecodeGraph, Sampler
+        from .kv_cache import KVCache
+
+        sampler = Sampler(temperature, top_k, eos_token_id)
+        if int(sync_every) != sync_every or sync_every < 1:
+            raise ValueError("generate(sync_every=...) needs an integer >= 1")
+        if x.dim() == 1:
+            x = x.unsqueeze(0)
+        B, P = x.shape
+        use_graph = graph is not False and graph is not None
+        dg = None
+        if weights is not None and not use_graph:
+            raise ValueError("generate(weights=...) needs graph=True or a DecodeGraph: only graph steps read FP8 weights")
+        if isinstance(graph, DecodeGraph):
+            if graph.model is not self:
+                raise ValueError("the DecodeGraph belongs to a different model")
+            if graph.cache.batch != B:
+                raise ValueError(f"batch {B} does not match the DecodeGraph's {graph.cache.batch}")
+            if graph.sampler != sampler:
+                raise ValueError("generate(sample_on_device=True, graph=<DecodeGraph>) needs a DecodeGraph built with "
+                                 "sampler=Sampler(temperature, top_k, eos_token_id) of this call")
+            dg = graph
+        elif use_graph and graph is not True:
+            raise ValueError("graph must be a bool or a DecodeGraph")
+        elif use_graph and not self.lm_head.weight.is_cuda:
+            raise ValueError("generate(graph=True) captures a HIP graph: the model must be on a GPU")
+        if max_new_tokens <= 0:
+            return x[:, P:]
+        L = self.context_length
+        u = torch.rand(max_new_tokens, B, device=x.device, generator=generator)
+        if dg is not None:
+            cache = dg.cache
+            cache.reset()
+        else:
+            w = self.lm_head.weight
+            dev = w.device.type
+            cdt = torch.get_autocast_dtype(dev) if torch.is_autocast_enabled(dev) else w.dtype
+            cache = KVCache(self, B, device=w.device, dtype=cdt, fp8=kv_fp8)
+        eos = eos_token_id
+
+        def pick(logits, s, done):  # token s of every row, (B, 1); a row that has ended stays at eos
+            t = ops.sample_logits(logits[:, -1], u[s], temperature, top_k)
+            if eos is not None:
+                if done is not None:
+                    t = torch.where(done, torch.full_like(t, eos), t)
+                done = (t == eos) if done is None else done | (t == eos)
+            return t[:, None], done
+
+        # token 0: the prefill on the prompt's last context_length tokens
+        logits = self.forward_cached(x[:, -L:] if P > L else x, cache)
+        tok, done = pick(logits, 0, None)
+        out = tok
+        # cached steps while the sequence fits the window (and the cache)
+        n_cached = min(max_new_tokens - 1, min(cache.max_len, L) - cache.length) if P <= L else 0
+        finished = False
+        if n_cached > 0 and use_graph:
+            if dg is None:
+                dg = DecodeGraph(self, cache, capture=True, weights=weights, sampler=sampler)
+            dg.begin(tok, 1 + n_cached, table=u[:1 + n_cached])
+            while dg._step < 1 + n_cached and not finished:
+                dg.advance(min(sync_every, 1 + n_cached - dg._step))
+                finished = dg.all_done()
+            out = dg.tokens()
+            done = dg.done != 0 if eos is not None else None
+        elif n_cached > 0:
+            toks = [tok]
+            for s in range(1, 1 + n_cached):
+                tok, done = pick(self.forward_cached(tok, cache), s, done)
+                toks.append(tok)
+                if eos is not None and s % sync_every == 0 and bool(done.all().item()):
+                    finished = True
+                    break
+            out = torch.cat(toks, dim=-1)
+        # the window is full (and slides from here on): full recomputation
+        if out.size(1) < max_new_tokens and not finished:
+            seq = torch.cat((x, out), dim=-1)
+            for s in range(out.size(1), max_new_tokens):
+                tok, done = pick(self.forward(seq[:, -L:] if seq.size(1) > L else seq), s, done)
+                seq = torch.cat((seq, tok), dim=-1)
+                if eos is not None and s % sync_every == 0 and bool(done.all().item()):
+                    break
+            out = seq[:, P:]
+        if eos is None:
+            return out
+        hit = out == eos
+        ended = hit.any(dim=-1)
+        first = torch.where(ended, hit.to(torch.int8).argmax(dim=-1), out.size(1))  # the first eos of each row
+        if B == 1:
+            return out[:, :int(first[0])]
+        return out[:, :int(first.max()) + 1] if bool(ended.all()) else out
 
     @classmethod
     def from_pretrained(cls, pretrained_model_path: str, map_location=None):

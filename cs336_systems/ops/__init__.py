@@ -17,6 +17,7 @@ from .flash_attention import (
 )
 from .rmsnorm import add_rmsnorm, add_rmsnorm_ref, rmsnorm, rmsnorm_ref
 from .rope import rope, rope_ref
+from .sample import sample_advance, sample_advance_ref, sample_logits, sample_logits_ref
 from .skinny import (quantize_fp8_rows, quantize_fp8_rows_, skinny_linear, skinny_linear_fp8, skinny_linear_fp8_ref,
                      skinny_linear_ref)
 from .swiglu import silu, silu_mul, silu_mul_ref
@@ -59,6 +60,10 @@ __all__ = [
     "rmsnorm_ref",
     "rope",
     "rope_ref",
+    "sample_advance",
+    "sample_advance_ref",
+    "sample_logits",
+    "sample_logits_ref",
     "quantize_fp8_rows",
     "quantize_fp8_rows_",
     "skinny_linear",

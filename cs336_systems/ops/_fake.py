@@ -223,3 +223,14 @@ if hasattr(torch.ops.cs336, "gemm_skinny"):  # (absent from libraries built befo
         @register_fake("cs336::gemm_skinny_w8")
         def _gemm_skinny_w8(x, wq, scale, out):
             return None
+
+
+if hasattr(torch.ops.cs336, "sample_logits"):  # (absent from libraries built before the fused sampler: A/B baselines)
+
+    @register_fake("cs336::sample_logits")
+    def _sample_logits(logits, u, temperature, top_k):
+        return logits.new_empty((logits.shape[0],), dtype=torch.int64)
+
+    @register_fake("cs336::sample_advance")
+    def _sample_advance(logits, u_table, step, temperature, top_k, eos_id, tok, out, done):
+        return None

@@ -1903,7 +1903,88 @@ void gemm_skinny_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor&
   cs336::gemm_skinny(p, cs336::SkinnyFormat::E4M3, to_dtype(x), stream());
 }
 
+// ------------------------------------------------------------------------------------------
+// Temperature / top-k sampler (csrc/ops/sample.hip): one token per row of logits (B, V) from one
+// caller-drawn uniform per row. sample_advance is the same inside a captured decode step.
+// ------------------------------------------------------------------------------------------
+static cs336::SampleParams sample_params(const char* op, const at::Tensor& logits, const at::Tensor& u, double temperature,
+                                         int64_t top_k) {
+  check_cuda(logits, "logits");
+  check_cuda(u, "u");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "cs336: ", op, " takes logits (B, V) with a contiguous last dim");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V <= (int64_t(1) << 30), "cs336: ", op, " takes 1 <= V <= 2^30 (got ", V, ")");
+  TORCH_CHECK(B <= (int64_t(1) << 30), "cs336: ", op, " batch too large");
+  TORCH_CHECK(B <= 1 || logits.stride(0) >= 0, "cs336: ", op, " logits row stride must not be negative");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(logits.data_ptr()) % logits.element_size()) == 0,
+              "cs336: ", op, " logits must be element aligned");
+  TORCH_CHECK(u.scalar_type() == at::kFloat && u.is_contiguous() && u.device() == logits.device(),
+              "cs336: ", op, " u must be contiguous fp32 on the logits' device");
+  TORCH_CHECK(temperature > 0, "cs336: ", op, " needs temperature > 0");
+  TORCH_CHECK(top_k >= 0, "cs336: ", op, " needs top_k >= 0");
+  cs336::SampleParams p;
+  p.logits = logits.data_ptr();
+  p.row_stride = B <= 1 ? 0 : logits.stride(0);
+  p.u = u.data_ptr<float>();
+  p.inv_temperature = (float)(1.0 / temperature);
+  p.B = (int)B; p.V = (int)V;
+  p.top_k = top_k >= V ? 0 : (int)top_k;
+  p.out = nullptr;
+  p.step = nullptr;
+  p.S = 0;
+  p.eos_id = -1;
+  p.tok = nullptr;
+  p.done = nullptr;
+  return p;
+}
+
+at::Tensor sample_logits(const at::Tensor& logits, const at::Tensor& u, double temperature, int64_t top_k) {
+  cs336::SampleParams p = sample_params("sample_logits", logits, u, temperature, top_k);
+  TORCH_CHECK(u.dim() == 1 && u.size(0) == p.B, "cs336: sample_logits takes u (B,)");
+  const DType t = to_dtype(logits);
+  c10::DeviceGuard g(logits.device());
+  at::Tensor out = at::empty({(int64_t)p.B}, logits.options().dtype(at::kLong));
+  p.out = out.data_ptr<int64_t>();
+  cs336::sample(p, t, stream());
+  return out;
+}
+
+void sample_advance(const at::Tensor& logits, const at::Tensor& u_table, const at::Tensor& step, double temperature,
+                    int64_t top_k, int64_t eos_id, at::Tensor& tok, at::Tensor& out, at::Tensor& done) {
+  cs336::SampleParams p = sample_params("sample_advance", logits, u_table, temperature, top_k);
+  check_cuda(step, "step");
+  check_cuda(tok, "tok");
+  check_cuda(out, "out");
+  check_cuda(done, "done");
+  TORCH_CHECK(u_table.dim() == 2 && u_table.size(1) == p.B, "cs336: sample_advance takes u_table (S, B)");
+  const int64_t S = u_table.size(0);
+  TORCH_CHECK(S <= (int64_t(1) << 30), "cs336: sample_advance table too long");
+  TORCH_CHECK(step.scalar_type() == at::kInt && step.numel() == 1, "cs336: sample_advance step must be int32 with one element");
+  TORCH_CHECK(tok.scalar_type() == at::kLong && tok.numel() == p.B && tok.is_contiguous(),
+              "cs336: sample_advance tok must be contiguous int64 (B, 1)");
+  TORCH_CHECK(out.scalar_type() == at::kLong && out.dim() == 2 && out.size(0) == p.B && out.size(1) == S && out.is_contiguous(),
+              "cs336: sample_advance out must be contiguous int64 (B, S)");
+  TORCH_CHECK(done.scalar_type() == at::kInt && done.dim() == 1 && done.size(0) == p.B && done.is_contiguous(),
+              "cs336: sample_advance done must be contiguous int32 (B,)");
+  TORCH_CHECK(step.device() == logits.device() && tok.device() == logits.device() && out.device() == logits.device() &&
+                  done.device() == logits.device(),
+              "cs336: sample_advance tensors must be on one device");
+  const DType t = to_dtype(logits);
+  c10::DeviceGuard g(logits.device());
+  p.step = step.data_ptr<int>();
+  p.S = (int)S;
+  p.eos_id = eos_id;
+  p.tok = tok.data_ptr<int64_t>();
+  p.out = out.data_ptr<int64_t>();
+  p.done = done.data_ptr<int>();
+  cs336::sample(p, t, stream());
+}
+
 TORCH_LIBRARY(cs336, m) {
+  m.def("sample_logits(Tensor logits, Tensor u, float temperature, int top_k) -> Tensor");
+  m.def(
+      "sample_advance(Tensor logits, Tensor u_table, Tensor step, float temperature, int top_k, int eos_id, "
+      "Tensor(a!) tok, Tensor(b!) out, Tensor(c!) done) -> ()");
   m.def("gemm_skinny_w8(Tensor x, Tensor wq, Tensor scale, Tensor(a!) out) -> ()");
   m.def("gemm_skinny_w8_ok(int M, int N, int K, int elem_size) -> bool", &gemm_skinny_w8_ok);
   m.def("gemm_skinny(Tensor x, Tensor w, Tensor(a!) out) -> ()");
@@ -1998,6 +2079,8 @@ TORCH_LIBRARY(cs336, m) {
 }
 
 TORCH_LIBRARY_IMPL(cs336, CUDA, m) {
+  m.impl("sample_logits", &sample_logits);
+  m.impl("sample_advance", &sample_advance);
   m.impl("gemm_skinny_w8", &gemm_skinny_w8);
   m.impl("gemm_skinny", &gemm_skinny);
   m.impl("fa_decode", &fa_decode);

@@ -378,4 +378,26 @@ struct SkinnyParams {
 bool gemm_skinny_ok(SkinnyFormat f, int64_t M, int64_t N, int64_t K, int64_t elem_size);
 void gemm_skinny(const SkinnyParams& p, SkinnyFormat f, DType t, hipStream_t s);
 
+// ---- temperature / top-k sampler (csrc/ops/sample.hip) ----
+// One token per row of logits (B, V; bf16 / fp16 / fp32 (DType), contiguous last dim, any element-aligned
+// row stride >= 0, 1 <= V <= 2^30) from one caller-supplied uniform u in [0, 1) per row; the rule is in
+// the kernel's header. top_k: 0 = no filter, else 1 <= top_k < V. step == nullptr: u is (B,), out (B,).
+// step != nullptr (sample_advance): s = step[0], u is the (S, B) table, out is (B, S), tok (B,), done (B,);
+// row b writes tok[b] and out[b, s] (eos_id where done[b]), sets done[b] when the token is eos_id
+// (eos_id < 0: never), and s outside [0, S) stores nothing. step itself is only read.
+struct SampleParams {
+  const void* logits;
+  int64_t row_stride;  // elements
+  const float* u;
+  float inv_temperature;
+  int B, V, top_k;
+  int64_t* out;
+  const int* step;
+  int S;
+  int64_t eos_id;
+  int64_t* tok;
+  int* done;
+};
+void sample(const SampleParams& p, DType t, hipStream_t s);
+
 }  // namespace cs336
