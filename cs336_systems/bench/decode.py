@@ -13,19 +13,23 @@ M 1 / 8 / 16, bf16, under the same ``do_bench`` protocol: us and GB/s of W bytes
 HBM rate, with ``torch.mm`` on the same operands alongside. ``--fp8`` adds, per row, the FP8 weight-only
 kernel ``cs336::gemm_skinny_w8`` (the same file, e4m3 weight format) on ``quantize_fp8_rows(w)``: median and
 q20-q80 over the same 50 flushed calls, GB/s of FP8 bytes, and the ratio to the bf16 skinny kernel of
-the same run.
+the same run. ``--fp4`` adds the MXFP4 weight-only kernel ``cs336::gemm_skinny_w4``
+(``csrc/gemm/gemm_skinny_w4.hip``) on ``quantize_mxfp4_rows(w)`` the same way: median, q20-q80, GB/s of its own
+bytes (17/32 per weight), the ratio to the FP8 kernel (with ``--fp8``) and to the bf16 kernel of the same run,
+and a verdict against each by the spread rule.
 
 End to end: tokens/s of ``generate`` with ``use_cache=True`` against ``use_cache=False`` (a full
 forward over the window per token) and against ``use_cache=True, graph=True`` (the cached step
 replayed from a HIP graph over the skinny-M kernel), model ``xl`` held in bf16. ``--arms`` picks the
 arms (the uncached one takes minutes at context 4096); ``graph+fp8`` is the graph arm over
-``Fp8DecodeWeights`` (``generate(..., graph=True, weights=qw)``). The graph arms also report the replayed
+``Fp8DecodeWeights`` (``generate(..., graph=True, weights=qw)``) and ``graph+fp4`` over ``Mxfp4DecodeWeights``. The graph arms also report the replayed
 step alone (HIP events around 50 replays on a cache holding the prompt, truncated back every time).
 
     python -m cs336_systems.bench.decode --json profiles/decode_attention.json
     python -m cs336_systems.bench.decode --no-e2e --batch 8 --kv-len 4096
     python -m cs336_systems.bench.decode --no-kernel --skinny --arms cached graph --json profiles/decode_graph.json
     python -m cs336_systems.bench.decode --no-kernel --skinny --fp8 --arms graph graph+fp8 --json profiles/decode_fp8.json
+    python -m cs336_systems.bench.decode --no-kernel --skinny --fp8 --fp4 --arms graph graph+fp8 graph+fp4 --json profiles/decode_fp4.json
 
 Chunk tables (``--chunk``): ``ops.decode_attention_chunk`` (``csrc/flash_attn/fa_decode_chunk.hip``) at
 n in {1, 2, 4, 8, 16} query rows over the same (B, H, d, kv_len) points: us, GB/s of K+V bytes (read
@@ -243,7 +247,7 @@ def skinny_shapes(model_size: str) -> list[tuple[str, int, int]]:
 
 
 def skinny_row(model_size: str, name: str, M: int, N: int, K: int, warmup: int = 10, rep: int = 50,
-               fp8: bool = False) -> dict:
+               fp8: bool = False, fp4: bool = False) -> dict:
     from ..ops import gemm
 
     dev, dt = "cuda", torch.bfloat16
@@ -281,6 +285,21 @@ def skinny_row(model_size: str, name: str, M: int, N: int, K: int, warmup: int =
         ref = ops.skinny_linear_fp8_ref(x, wq, scale)
         row["fp8_max_abs_diff_vs_ref"] = (out.float() - ref.float()).abs().max().item()
         del wq, scale
+    if fp4:
+        wq, scale = ops.quantize_mxfp4_rows(w)
+        assert gemm.skinny_w4_ok(x, wq, scale)
+        q_bytes = float(wq.numel() + scale.numel())
+        row["fp4_us"], row["fp4_us_q20"], row["fp4_us_q80"] = t(lambda: torch.ops.cs336.gemm_skinny_w4(x, wq, scale, out))
+        row["fp4_mbytes"] = q_bytes / 2**20
+        row["fp4_gbs"] = q_bytes / (row["fp4_us"] * 1e-6) / 1e9
+        row["fp4_hbm_frac"] = row["fp4_gbs"] / HBM_ACHIEVABLE_GBS
+        for base in ("skinny",) + (("fp8",) if fp8 else ()):  # below 1: the MXFP4 kernel is faster
+            row[f"fp4_vs_{base}"] = row["fp4_us"] / row[f"{base}_us"]
+            row[f"fp4_verdict_vs_{base}"] = ("faster" if row["fp4_us_q80"] < row[f"{base}_us_q20"] else
+                                             "slower" if row["fp4_us_q20"] > row[f"{base}_us_q80"] else "same")
+        ref = ops.skinny_linear_mxfp4_ref(x, wq, scale)
+        row["fp4_max_abs_diff_vs_ref"] = (out.float() - ref.float()).abs().max().item()
+        del wq, scale
     del x, w, out
     torch.cuda.empty_cache()
     return row
@@ -315,11 +334,12 @@ def sample_row(B: int, V: int, top_k, warmup: int = 10, rep: int = 50) -> dict:
 
 ARMS = {"cached": dict(use_cache=True), "uncached": dict(use_cache=False), "graph": dict(use_cache=True, graph=True),
         "graph+fp8": dict(use_cache=True, graph=True),  # (+ weights=Fp8DecodeWeights(model), built per model)
+        "graph+fp4": dict(use_cache=True, graph=True),  # (+ weights=Mxfp4DecodeWeights(model))
         "graph+kv8": dict(use_cache=True, graph=True, kv_fp8=True),
         "graph+fp8+kv8": dict(use_cache=True, graph=True, kv_fp8=True),  # (+ weights)
         "graph+sample": dict(use_cache=True, graph=True, sample_on_device=True),
         "graph+fp8+sample": dict(use_cache=True, graph=True, sample_on_device=True)}  # (+ weights)
-ARM_KEYS = {"graph": "cached_graph", "graph+fp8": "cached_graph_fp8", "graph+kv8": "cached_graph_kv8",
+ARM_KEYS = {"graph": "cached_graph", "graph+fp8": "cached_graph_fp8", "graph+fp4": "cached_graph_fp4", "graph+kv8": "cached_graph_kv8",
             "graph+fp8+kv8": "cached_graph_fp8_kv8"}
 
 
@@ -355,9 +375,15 @@ def e2e_row(model_size: str, ctx: int, B: int, prompt: int, new: int, arms=("cac
     model = build_model(model_size, ctx, device="cuda").to(torch.bfloat16).eval()
     x = torch.randint(0, model.vocab_size, (B, prompt), device="cuda")
     row = dict(model=model_size, context_length=ctx, B=B, prompt=prompt, new_tokens=new, dtype="bf16")
-    qw = None
+    qw = q4 = None
     for arm in arms:
         kw = dict(ARMS[arm])
+        if arm == "graph+fp4":
+            from ..models import Mxfp4DecodeWeights
+
+            q4 = q4 or Mxfp4DecodeWeights(model)
+            kw["weights"] = q4
+            row["fp4_weight_mbytes"] = q4.nbytes / 2**20
         if arm in ("graph+fp8", "graph+fp8+kv8", "graph+fp8+sample"):
             from ..models import Fp8DecodeWeights
 
@@ -398,6 +424,14 @@ def e2e_row(model_size: str, ctx: int, B: int, prompt: int, new: int, arms=("cac
     if "cached_graph_s" in row and "cached_graph_fp8_s" in row:
         row["fp8_speedup_vs_graph"] = row["cached_graph_s"] / row["cached_graph_fp8_s"]
         row["fp8_replay_vs_graph"] = row["cached_graph_fp8_replay_ms"] / row["cached_graph_replay_ms"]
+    for base in ("cached_graph", "cached_graph_fp8"):  # the MXFP4 step against the 16-bit and the FP8 step of this run
+        if "cached_graph_fp4_s" in row and f"{base}_s" in row:
+            tag = "graph" if base == "cached_graph" else "fp8"
+            row[f"fp4_speedup_vs_{tag}"] = row[f"{base}_s"] / row["cached_graph_fp4_s"]
+            row[f"fp4_replay_vs_{tag}"] = row["cached_graph_fp4_replay_ms"] / row[f"{base}_replay_ms"]
+            row[f"fp4_replay_verdict_vs_{tag}"] = (
+                "faster" if row["cached_graph_fp4_replay_ms_q80"] < row[f"{base}_replay_ms_q20"] else
+                "slower" if row["cached_graph_fp4_replay_ms_q20"] > row[f"{base}_replay_ms_q80"] else "same")
     for name, base in (("cached_graph_sample", "cached_graph"), ("cached_graph_fp8_sample", "cached_graph_fp8")):
         if f"{name}_s" in row and f"{base}_s" in row:
             row[f"{name}_vs_{base[7:]}"] = row[f"{name}_s"] / row[f"{base}_s"]  # below 1: sampling in the graph is faster
@@ -429,6 +463,7 @@ def main(argv=None):
     ap.add_argument("--model", default="xl")
     ap.add_argument("--skinny", action="store_true", help="the skinny-M GEMM table (xl and 2.7b projections)")
     ap.add_argument("--fp8", action="store_true", help="with --skinny: add the FP8 weight-only kernel to every row")
+    ap.add_argument("--fp4", action="store_true", help="with --skinny: add the MXFP4 weight-only kernel to every row")
     ap.add_argument("--kv-fp8", action="store_true",
                     help="add the FP8 KV cache kernels to every kernel / chunk row, and the end-to-end point "
                          "context 4096, B 8, prompt 2048 + 512")
@@ -484,7 +519,7 @@ def main(argv=None):
         for size in ("xl", "2.7b"):
             for name, N, K in skinny_shapes(size):
                 for M in SKINNY_M:
-                    r = skinny_row(size, name, M, N, K, rep=a.rep, fp8=a.fp8)
+                    r = skinny_row(size, name, M, N, K, rep=a.rep, fp8=a.fp8, fp4=a.fp4)
                     out["skinny"].append(r)
                     print(json.dumps(r), flush=True)
     if a.sample:

@@ -1,7 +1,7 @@
 from .configs import DEFAULT_THETA, DEFAULT_VOCAB, MODEL_CONFIGS, get_model_config, param_count, train_flops_per_token
 from .decode_graph import DecodeGraph, Sampler
 from .kv_cache import KVCache
-from .quantized import Fp8DecodeWeights
+from .quantized import Fp8DecodeWeights, Mxfp4DecodeWeights
 from .speculative import speculative_generate
 from .transformer import (
     BasicsTransformerLM,
@@ -34,6 +34,7 @@ __all__ = [
     "DecodeGraph",
     "Embedding",
     "Fp8DecodeWeights",
+    "Mxfp4DecodeWeights",
     "KVCache",
     "Linear",
     "RMSNorm",

@@ -32,7 +32,9 @@ kernel (the e4m3 weight format of ``csrc/gemm/gemm_skinny.hip``) at up to 16 row
 eager and the
 ``tokens=n`` step alike. Only the steps a ``DecodeGraph`` runs read FP8: the prefill is an ordinary
 ``forward_cached`` on the 16-bit weights. After an in-place weight update call ``qw.refresh()``, which
-requantizes in place; the next replay picks it up.
+requantizes in place; the next replay picks it up. An ``Mxfp4DecodeWeights`` is taken the same way: the
+step then reads the MXFP4 copy through ``csrc/gemm/gemm_skinny_w4.hip``; the weights object says which
+linear runs.
 
 An FP8 cache (``KVCache(fp8=True)``) needs no argument: the graph is tied to its cache, the step appends
 and reads quantized rows (``csrc/flash_attn/fa_decode_kv8.hip``, ``fa_decode_chunk_kv8.hip``) and nothing
@@ -143,7 +145,7 @@ class DecodeGraph:
         """The step both modes run: the decode (or, for ``tokens > 1``, chunk) branch of
         ``forward_cached`` (also on an empty cache, where the warm-up's rows land at index 0, unread)
         with the fixed attention bound."""
-        with gemm.skinny_decode(fp8=self.weights):
+        with gemm.skinny_decode(weights=self.weights):
             return self.model._forward_cached(tok, self.cache, max(self.cache.length, 1), self.cache.max_len)
 
     @torch.no_grad()

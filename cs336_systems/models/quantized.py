@@ -1,4 +1,4 @@
-"""FP8 weight-only copies of a model's projection matrices for the decode step.
+"""FP8 and MXFP4 weight-only copies of a model's projection matrices for the decode step.
 
 A replayed decode token streams every projection matrix from HBM once; on the large matrices its
 time is the weight bytes. ``Fp8DecodeWeights(model)`` keeps a second copy of those matrices as OCP
@@ -12,6 +12,12 @@ The copy is used only where it is asked for: ``DecodeGraph(model, cache, weights
 which a projection whose 16-bit weight is in ``qw``'s table reads the FP8 copy. The prefill and
 every other forward keep reading the 16-bit weights, and both copies stay alive: this trades memory
 for decode speed, it does not save memory.
+
+``Mxfp4DecodeWeights(model)`` is the same object in the OCP MXFP4 format (``ops.quantize_mxfp4_rows``: two
+e2m1 codes per byte and one e8m0 power-of-two scale per 32 values, 17/32 of a byte per weight), read by
+``ops.skinny_linear_mxfp4``. The two classes share everything but the format: ``_DecodeWeights`` holds the
+tables, and a format supplies its buffers, quantizer, dequantizer and linear. ``gemm.skinny_decode`` and
+the model's layers call ``qw.linear``, so the weights object says which kernel runs.
 """
 
 from __future__ import annotations
@@ -19,11 +25,13 @@ from __future__ import annotations
 import torch
 
 from . import fused
-from ..ops.skinny import quantize_fp8_rows_
+from ..ops import skinny
 
 
-class Fp8DecodeWeights:
-    """``qw = Fp8DecodeWeights(model)`` for a ``BasicsTransformerLM`` held in bf16 or fp16.
+class _DecodeWeights:
+    """What the quantized copies share: ``qw = Fp8DecodeWeights(model)`` / ``Mxfp4DecodeWeights(model)`` for
+    a ``BasicsTransformerLM`` held in bf16 or fp16. A format defines ``K_UNIT`` and ``WHY`` (K must be a
+    multiple of the kernel's W load), ``_alloc``, ``_quantize_``, ``_dequantize`` and ``linear``.
 
     ``qw.lookup(w)`` maps the 16-bit operand tensor a projection hands to ``gemm.mm_nt`` -- the grouped
     QKV / W1|W3 view, or a single parameter -- to its ``(wq, scale)``. The table is keyed on address and
@@ -38,7 +46,7 @@ class Fp8DecodeWeights:
     def __init__(self, model):
         if getattr(model, "tensor_parallel", None) is not None or any(
                 layer.attn.context_parallel is not None for layer in model.layers):
-            raise NotImplementedError("Fp8DecodeWeights does not support tensor / context parallelism")
+            raise NotImplementedError(f"{type(self).__name__} does not support tensor / context parallelism")
         self.model = model
         self._groups: list[tuple[list[torch.Tensor], torch.Tensor, torch.Tensor]] = []
         self._table: dict[tuple, tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = {}
@@ -55,15 +63,14 @@ class Fp8DecodeWeights:
         p0 = params[0]
         for p in params:
             if p.dtype not in (torch.bfloat16, torch.float16):
-                raise ValueError(f"Fp8DecodeWeights needs the model held in bf16 or fp16: {name} is {p.dtype}")
+                raise ValueError(f"{type(self).__name__} needs the model held in bf16 or fp16: {name} is {p.dtype}")
             if p.dim() != 2 or p.shape[1] != p0.shape[1] or p.dtype != p0.dtype or p.device != p0.device:
                 raise ValueError(f"{name}: the matrices of a group must share width, dtype and device")
         k = p0.shape[1]
-        if k < 16 or k % 16:
-            raise ValueError(f"{name}: K = {k} is not a multiple of 16 (the FP8 kernel loads 16 k at a time)")
+        if k < self.K_UNIT or k % self.K_UNIT:
+            raise ValueError(f"{name}: K = {k} is not a multiple of {self.K_UNIT} ({self.WHY})")
         rows = sum(p.shape[0] for p in params)
-        wq = torch.empty(rows, k, dtype=torch.float8_e4m3fn, device=p0.device)
-        scale = torch.empty(rows, dtype=torch.float32, device=p0.device)
+        wq, scale = self._alloc(rows, k, p0.device)
         held = [p.detach() for p in params]
         self._groups.append((held, wq, scale))
         # each matrix on its own (the ungrouped and the CPU paths multiply by them one at a time) ...
@@ -89,12 +96,12 @@ class Fp8DecodeWeights:
         return e[1], e[2]
 
     @torch.no_grad()
-    def refresh(self) -> "Fp8DecodeWeights":
+    def refresh(self):
         for held, wq, scale in self._groups:
             off = 0
             for t in held:
                 n = t.shape[0]
-                quantize_fp8_rows_(t, wq[off:off + n], scale[off:off + n])
+                self._quantize_(t, wq[off:off + n], scale[off:off + n])
                 off += n
         return self
 
@@ -104,7 +111,7 @@ class Fp8DecodeWeights:
                    for _, wq, scale in self._groups)
 
     def dequantized_state_dict(self, dtype: torch.dtype = torch.float32) -> dict[str, torch.Tensor]:
-        """The model's ``state_dict`` with every quantized matrix replaced by ``wq * scale`` in
+        """The model's ``state_dict`` with every quantized matrix replaced by its dequantized copy in
         ``dtype`` (the other entries cast to it): the exact model a quantized step approximates."""
         sd = {k: v.detach().to(dtype) for k, v in self.model.state_dict().items()}
         names = {p.data_ptr(): k for k, p in self.model.named_parameters()}
@@ -112,6 +119,56 @@ class Fp8DecodeWeights:
             off = 0
             for t in held:
                 n = t.shape[0]
-                sd[names[t.data_ptr()]] = wq[off:off + n].to(dtype) * scale[off:off + n].to(dtype)[:, None]
+                sd[names[t.data_ptr()]] = self._dequantize(wq[off:off + n], scale[off:off + n], dtype)
                 off += n
         return sd
+
+
+class Fp8DecodeWeights(_DecodeWeights):
+    """OCP e4m3 bytes with one fp32 scale per output row (``ops.quantize_fp8_rows``): ``wq`` (N, K)
+    ``float8_e4m3fn``, ``scale`` (N,); ``nbytes`` is elements + 4 bytes per row."""
+
+    K_UNIT = 16
+    WHY = "the FP8 kernel loads 16 k at a time"
+
+    @staticmethod
+    def _alloc(rows, k, device):
+        return (torch.empty(rows, k, dtype=torch.float8_e4m3fn, device=device),
+                torch.empty(rows, dtype=torch.float32, device=device))
+
+    @staticmethod
+    def _quantize_(w, wq, scale):
+        skinny.quantize_fp8_rows_(w, wq, scale)
+
+    @staticmethod
+    def _dequantize(wq, scale, dtype):
+        return wq.to(dtype) * scale.to(dtype)[:, None]
+
+    @staticmethod
+    def linear(x, wq, scale):
+        return skinny.skinny_linear_fp8(x, wq, scale)
+
+
+class Mxfp4DecodeWeights(_DecodeWeights):
+    """OCP MXFP4 (``ops.quantize_mxfp4_rows``): ``wq`` (N, K/2) uint8 of two e2m1 codes, ``scale`` (N, K/32)
+    uint8 e8m0; every K a multiple of 32; ``nbytes`` is elements x 17/32."""
+
+    K_UNIT = 32
+    WHY = "an MXFP4 block is 32 k"
+
+    @staticmethod
+    def _alloc(rows, k, device):
+        return (torch.empty(rows, k // 2, dtype=torch.uint8, device=device),
+                torch.empty(rows, k // 32, dtype=torch.uint8, device=device))
+
+    @staticmethod
+    def _quantize_(w, wq, scale):
+        skinny.quantize_mxfp4_rows_(w, wq, scale)
+
+    @staticmethod
+    def _dequantize(wq, scale, dtype):
+        return skinny.dequantize_mxfp4_rows(wq, scale, dtype)
+
+    @staticmethod
+    def linear(x, wq, scale):
+        return skinny.skinny_linear_mxfp4(x, wq, scale)

@@ -77,9 +77,9 @@ class Linear(nn.Module):
             return y.view(*x.shape[:-1], y.shape[-1])
         if x.is_cuda:
             return fused.fused_linear(x, self.weight)
-        hit = _gemm.fp8_lookup(self.weight)  # inside gemm.skinny_decode(fp8=...): the quantized copy
-        if hit is not None:
-            return ops.skinny_linear_fp8(x, *hit)
+        y = _gemm.quantized_linear(x, self.weight)  # inside gemm.skinny_decode(weights=...): the quantized copy
+        if y is not None:
+            return y
         return F.linear(x, self.weight)
 
     def extra_repr(self):
@@ -732,8 +732,8 @@ class BasicsTransformerLM(nn.Module):
         and batch size (its cache is reset and prefilled), which saves the capture per call.
         Sampling stays eager.
 
-        ``weights=qw`` (an ``Fp8DecodeWeights`` of this model, with ``graph=True``): the graph is built
-        with the FP8 weight copy, so every replayed step streams 8-bit weights. The prefill is
+        ``weights=qw`` (an ``Fp8DecodeWeights`` or ``Mxfp4DecodeWeights`` of this model, with ``graph=True``):
+        the graph is built with the quantized weight copy, so every replayed step streams 8-bit (4-bit) weights. The prefill is
         unchanged and reads the 16-bit weights, as do the sliding-window steps once the window is
         full. With ``graph=<DecodeGraph>`` the graph's own weights are used; ``weights=`` without a
         graph raises.

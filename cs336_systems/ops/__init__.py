@@ -18,8 +18,9 @@ from .flash_attention import (
 from .rmsnorm import add_rmsnorm, add_rmsnorm_ref, rmsnorm, rmsnorm_ref
 from .rope import rope, rope_ref
 from .sample import sample_advance, sample_advance_ref, sample_logits, sample_logits_ref
-from .skinny import (quantize_fp8_rows, quantize_fp8_rows_, skinny_linear, skinny_linear_fp8, skinny_linear_fp8_ref,
-                     skinny_linear_ref)
+from .skinny import (dequantize_mxfp4_rows, quantize_fp8_rows, quantize_fp8_rows_, quantize_mxfp4_rows,
+                     quantize_mxfp4_rows_, skinny_linear, skinny_linear_fp8, skinny_linear_fp8_ref, skinny_linear_mxfp4,
+                     skinny_linear_mxfp4_ref, skinny_linear_ref)
 from .swiglu import silu, silu_mul, silu_mul_ref
 
 __all__ = [
@@ -64,11 +65,16 @@ __all__ = [
     "sample_advance_ref",
     "sample_logits",
     "sample_logits_ref",
+    "dequantize_mxfp4_rows",
     "quantize_fp8_rows",
     "quantize_fp8_rows_",
+    "quantize_mxfp4_rows",
+    "quantize_mxfp4_rows_",
     "skinny_linear",
     "skinny_linear_fp8",
     "skinny_linear_fp8_ref",
+    "skinny_linear_mxfp4",
+    "skinny_linear_mxfp4_ref",
     "skinny_linear_ref",
     "silu",
     "silu_mul",

@@ -224,6 +224,12 @@ if hasattr(torch.ops.cs336, "gemm_skinny"):  # (absent from libraries built befo
         def _gemm_skinny_w8(x, wq, scale, out):
             return None
 
+    if hasattr(torch.ops.cs336, "gemm_skinny_w4"):  # (absent from libraries built before the MXFP4 weights)
+
+        @register_fake("cs336::gemm_skinny_w4")
+        def _gemm_skinny_w4(x, wq, scale, out):
+            return None
+
 
 if hasattr(torch.ops.cs336, "sample_logits"):  # (absent from libraries built before the fused sampler: A/B baselines)
 

@@ -293,11 +293,11 @@ def gemm8_rope(x: torch.Tensor, w: torch.Tensor, cos: torch.Tensor, sin: torch.T
 
 SKINNY_MAX_M = 16  # rows the skinny-M kernel takes (one MFMA tile of batch rows)
 _SKINNY = False
-_FP8 = None  # the quantized weights (models/quantized.py) of the innermost skinny_decode(fp8=...)
+_FP8 = None  # the quantized weights (models/quantized.py, either format) of the innermost skinny_decode(...)
 
 
 @contextmanager
-def skinny_decode(fp8=None):
+def skinny_decode(fp8=None, weights=None):
     """While active, :func:`mm_nt` sends calls with at most ``SKINNY_MAX_M`` rows that
     :func:`skinny_ok` takes to the weight-streaming kernel (``csrc/gemm/gemm_skinny.hip``): the
     M = batch projections of a decode step. Off by default; outside it ``mm_nt`` is unchanged.
@@ -306,9 +306,15 @@ def skinny_decode(fp8=None):
     ``ops.skinny_linear_fp8`` on the quantized copy instead -- the FP8 kernel
     (the e4m3 weight format of ``csrc/gemm/gemm_skinny.hip``) at 16 rows or fewer, for every such shape:
     :func:`skinny_routed`'s exception was measured for the 16-bit kernel against ``torch.mm`` and
-    does not apply to it. A ``w`` that is not in the table takes the path above."""
+    does not apply to it. A ``w`` that is not in the table takes the path above.
+
+    ``weights=qw`` is the same argument under a neutral name: an ``Fp8DecodeWeights`` or an
+    ``Mxfp4DecodeWeights``. The object says which linear runs (its ``linear(x, wq, scale)``:
+    ``ops.skinny_linear_fp8`` or ``ops.skinny_linear_mxfp4``); give one of the two keywords."""
     global _SKINNY, _FP8
-    prev, _SKINNY, prev_fp8, _FP8 = _SKINNY, True, _FP8, fp8
+    if fp8 is not None and weights is not None:
+        raise ValueError("skinny_decode takes fp8= or weights=, not both")
+    prev, _SKINNY, prev_fp8, _FP8 = _SKINNY, True, _FP8, fp8 if weights is None else weights
     try:
         yield
     finally:
@@ -317,8 +323,52 @@ def skinny_decode(fp8=None):
 
 def fp8_lookup(w: torch.Tensor):
     """``(wq, scale)`` for the 16-bit weight ``w`` inside ``skinny_decode(fp8=qw)`` when ``qw`` holds
-    its quantized copy, else None."""
+    its quantized copy (in ``qw``'s format, FP8 or MXFP4), else None."""
     return None if _FP8 is None else _FP8.lookup(w)
+
+
+def quantized_linear(x: torch.Tensor, w: torch.Tensor):
+    """``x @ dq(w).T`` on the quantized copy of the 16-bit weight ``w`` inside ``skinny_decode(weights=qw)``
+    when ``qw`` holds one -- the linear of ``qw``'s format, leading dims of ``x`` kept -- else None."""
+    hit = fp8_lookup(w)
+    return None if hit is None else _FP8.linear(x, *hit)
+
+
+def skinny_w4_ok(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> bool:
+    """Whether ``cs336::gemm_skinny_w4`` takes ``x @ dq.T``: GPU bf16 / fp16 ``x`` (M, K) of at most 16
+    rows, ``wq`` (N, K/2) uint8 / float4_e2m1fn_x2, ``scale`` (N, K/32) uint8 / float8_e8m0fnu with a
+    contiguous last dim and rows at least K/32 apart, K % 32 == 0, row-major operands with 16-B aligned
+    rows (``wq`` rows at least K/2 apart)."""
+    return (
+        x.is_cuda
+        and wq.is_cuda
+        and scale.is_cuda
+        and x.dtype in (torch.bfloat16, torch.float16)
+        and wq.dtype in (torch.uint8, torch.float4_e2m1fn_x2)
+        and scale.dtype in (torch.uint8, torch.float8_e8m0fnu)
+        and x.dim() == 2
+        and wq.dim() == 2
+        and scale.dim() == 2
+        and x.shape[1] == 2 * wq.shape[1]
+        and x.shape[1] % 32 == 0
+        and tuple(scale.shape) == (wq.shape[0], x.shape[1] // 32)
+        and scale.stride(1) == 1
+        and (scale.shape[0] == 1 or scale.stride(0) >= scale.shape[1])
+        and _aligned_rows(x)
+        and x.stride(0) >= 0
+        and wq.stride(1) == 1
+        and wq.stride(0) % 16 == 0
+        and wq.data_ptr() % 16 == 0
+        and (wq.shape[0] == 1 or wq.stride(0) >= wq.shape[1])
+        and ext_available()
+        and ops().gemm_skinny_w4_ok(x.shape[0], wq.shape[0], x.shape[1], x.element_size())
+    )
+
+
+def skinny_w4_mm(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    out = torch.empty(x.shape[0], wq.shape[0], device=x.device, dtype=x.dtype)
+    ops().gemm_skinny_w4(x, wq, scale, out)
+    return out
 
 
 def skinny_w8_ok(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> bool:
@@ -391,11 +441,9 @@ def skinny_mm(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 def mm_nt(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """``x @ w.T`` (forward of a linear layer; the input gradient through a Wᵀ shadow)."""
     if _FP8 is not None:
-        hit = _FP8.lookup(w)
-        if hit is not None:
-            from .skinny import skinny_linear_fp8
-
-            return skinny_linear_fp8(x, *hit)
+        y = quantized_linear(x, w)  # the weights object's own linear: FP8 or MXFP4
+        if y is not None:
+            return y
     if (_SKINNY and x.shape[0] <= SKINNY_MAX_M and skinny_routed(x.shape[0], w.shape[0], x.shape[1])
             and skinny_ok(x, w)):
         return skinny_mm(x, w)

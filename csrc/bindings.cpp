@@ -1837,6 +1837,8 @@ int64_t fa_decode_kv8_splits(int64_t B, int64_t H, int64_t D, int64_t n, int64_t
 // Skinny-M GEMM for decode (csrc/gemm/gemm_skinny.hip), M <= 16, x / out bf16 or fp16:
 //   gemm_skinny:    out[M,N] = x[M,K] · w[N,K]ᵀ, w of x's dtype
 //   gemm_skinny_w8: out[M,N] = (x[M,K] · wq[N,K]ᵀ) * scale[N], wq e4m3 (or its uint8 view)
+//   gemm_skinny_w4: out[M,N] = x[M,K] · dq[N,K]ᵀ, dq the MXFP4 weight: wq (N, K/2) bytes of two e2m1 codes
+//                   (uint8 or float4_e2m1fn_x2), scale (N, K/32) e8m0 bytes (uint8 or float8_e8m0fnu)
 // ------------------------------------------------------------------------------------------
 bool gemm_skinny_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
   return cs336::gemm_skinny_ok(cs336::SkinnyFormat::W16, M, N, K, elem_size);
@@ -1845,11 +1847,17 @@ bool gemm_skinny_w8_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
   return cs336::gemm_skinny_ok(cs336::SkinnyFormat::E4M3, M, N, K, elem_size);
 }
 
-// What the two ops check and fill alike; w's dtype (and scale) is the caller's. `op` and `wn` name the
-// op and its weight operand in the messages; kl is the format's k per 16-byte W load.
+bool gemm_skinny_w4_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
+  return cs336::gemm_skinny_ok(cs336::SkinnyFormat::MXFP4, M, N, K, elem_size);
+}
+
+// What the three ops check and fill alike; w's dtype (and scale) is the caller's. `op` and `wn` name the
+// op and its weight operand in the messages; kl is the format's k per 16-byte W load, wl the elements of
+// w's storage in one (MXFP4 packs two k per byte).
 static cs336::SkinnyParams skinny_params(const char* op, const char* wn, cs336::SkinnyFormat f, const at::Tensor& x,
                                          const at::Tensor& w, at::Tensor& out) {
   const int64_t kl = cs336::skinny_k_per_load(f);
+  const int64_t kpw = f == cs336::SkinnyFormat::MXFP4 ? 2 : 1, wl = kl / kpw;
   check_cuda(x, "x");
   check_cuda(w, wn);
   check_cuda(out, "out");
@@ -1858,13 +1866,14 @@ static cs336::SkinnyParams skinny_params(const char* op, const char* wn, cs336::
   TORCH_CHECK(out.scalar_type() == x.scalar_type(), "cs336: ", op, " x / out dtype mismatch");
   TORCH_CHECK(w.device() == x.device() && out.device() == x.device(), "cs336: ", op, " tensors must be on one device");
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(w.size(1) == K && out.size(0) == M && out.size(1) == N, "cs336: ", op, " shape mismatch");
+  TORCH_CHECK(w.size(1) * kpw == K && out.size(0) == M && out.size(1) == N, "cs336: ", op, " shape mismatch");
   TORCH_CHECK(M >= 1 && M <= 16, "cs336: ", op, " takes 1 <= M <= 16 (got ", M, ")");
   TORCH_CHECK(K >= kl && K % kl == 0, "cs336: ", op, " needs K % ", kl, " == 0 (got ", K, ")");
   TORCH_CHECK(cs336::gemm_skinny_ok(f, M, N, K, x.element_size()), "cs336: ", op, " extents exceed the kernel's 32-bit row / k indices");
   TORCH_CHECK(x.stride(1) == 1 && w.stride(1) == 1 && out.stride(1) == 1, "cs336: ", op, " operands must have a contiguous last dim");
   TORCH_CHECK(x.stride(0) % 8 == 0 && (M == 1 || x.stride(0) >= 0), "cs336: ", op, " x row stride must be a non-negative multiple of 8");
-  TORCH_CHECK(w.stride(0) % kl == 0 && (N == 1 || w.stride(0) >= K), "cs336: ", op, " ", wn, " row stride must be a multiple of ", kl, ", at least K");
+  TORCH_CHECK(w.stride(0) % wl == 0 && (N == 1 || w.stride(0) >= K / kpw), "cs336: ", op, " ", wn, " row stride must be a multiple of ", wl,
+              ", at least a row");
   TORCH_CHECK(M == 1 || out.stride(0) >= N, "cs336: ", op, " out rows must not overlap");
   TORCH_CHECK((reinterpret_cast<uintptr_t>(x.data_ptr()) % 16) == 0 && (reinterpret_cast<uintptr_t>(w.data_ptr()) % 16) == 0,
               "cs336: ", op, " x and ", wn, " must be 16-byte aligned");
@@ -1901,6 +1910,22 @@ void gemm_skinny_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor&
   p.scale = scale.data_ptr<float>();
   c10::DeviceGuard g(x.device());
   cs336::gemm_skinny(p, cs336::SkinnyFormat::E4M3, to_dtype(x), stream());
+}
+
+void gemm_skinny_w4(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
+  check_cuda(scale, "scale");
+  TORCH_CHECK(scale.dim() == 2, "cs336: gemm_skinny_w4 takes x (M, K), wq (N, K/2), scale (N, K/32), out (M, N)");
+  TORCH_CHECK(wq.scalar_type() == at::kByte || wq.scalar_type() == at::ScalarType::Float4_e2m1fn_x2, "cs336: gemm_skinny_w4 takes wq as uint8 or float4_e2m1fn_x2");
+  TORCH_CHECK(scale.scalar_type() == at::kByte || scale.scalar_type() == at::ScalarType::Float8_e8m0fnu, "cs336: gemm_skinny_w4 takes scale as uint8 or float8_e8m0fnu");
+  TORCH_CHECK(scale.device() == x.device(), "cs336: gemm_skinny_w4 tensors must be on one device");
+  cs336::SkinnyParams p = skinny_params("gemm_skinny_w4", "wq", cs336::SkinnyFormat::MXFP4, x, wq, out);
+  TORCH_CHECK(scale.size(0) == p.N && scale.size(1) == p.K / 32, "cs336: gemm_skinny_w4 scale must be (N, K/32) = (", p.N, ", ", p.K / 32, ")");
+  TORCH_CHECK(scale.stride(1) == 1 && (p.N == 1 || scale.stride(0) >= p.K / 32),
+              "cs336: gemm_skinny_w4 scale needs a contiguous last dim and rows at least K/32 apart");
+  p.bscale = static_cast<const uint8_t*>(scale.data_ptr());
+  p.ldbs = p.N == 1 ? 0 : scale.stride(0);
+  c10::DeviceGuard g(x.device());
+  cs336::gemm_skinny(p, cs336::SkinnyFormat::MXFP4, to_dtype(x), stream());
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1987,6 +2012,8 @@ TORCH_LIBRARY(cs336, m) {
       "Tensor(a!) tok, Tensor(b!) out, Tensor(c!) done) -> ()");
   m.def("gemm_skinny_w8(Tensor x, Tensor wq, Tensor scale, Tensor(a!) out) -> ()");
   m.def("gemm_skinny_w8_ok(int M, int N, int K, int elem_size) -> bool", &gemm_skinny_w8_ok);
+  m.def("gemm_skinny_w4(Tensor x, Tensor wq, Tensor scale, Tensor(a!) out) -> ()");
+  m.def("gemm_skinny_w4_ok(int M, int N, int K, int elem_size) -> bool", &gemm_skinny_w4_ok);
   m.def("gemm_skinny(Tensor x, Tensor w, Tensor(a!) out) -> ()");
   m.def("gemm_skinny_ok(int M, int N, int K, int elem_size) -> bool", &gemm_skinny_ok);
   m.def(
@@ -2082,6 +2109,7 @@ TORCH_LIBRARY_IMPL(cs336, CUDA, m) {
   m.impl("sample_logits", &sample_logits);
   m.impl("sample_advance", &sample_advance);
   m.impl("gemm_skinny_w8", &gemm_skinny_w8);
+  m.impl("gemm_skinny_w4", &gemm_skinny_w4);
   m.impl("gemm_skinny", &gemm_skinny);
   m.impl("fa_decode", &fa_decode);
   m.impl("kv_append_rope", &kv_append_rope);

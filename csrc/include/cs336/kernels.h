@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "skinny_format.h"
 
 namespace cs336 {
 
@@ -359,13 +360,15 @@ struct QuantizeRowsParams {
 };
 void kv_quantize_rows(const QuantizeRowsParams& p, DType t, hipStream_t s);
 
-// ---- skinny-M GEMM for decode, 16-bit or FP8 weights (csrc/gemm/gemm_skinny.hip) ----
+// ---- skinny-M GEMM for decode, 16-bit, FP8 or MXFP4 weights (csrc/gemm/gemm_skinny.hip, gemm_skinny_w4.hip) ----
 // W16:  out[M,N] = x[M,K] · w[N,K]ᵀ, w of x's type.
 // E4M3: out[M,N] = round(fp32(x[M,K] · w[N,K]ᵀ) * scale[N]), w OCP e4m3 bytes, scale fp32 per W row.
+// MXFP4: out[M,N] = round(fp32(x[M,K] · dq[N,K]ᵀ)), dq[n,k] = e2m1 code k of row n (two per byte of w, low
+//       nibble first) times 2^(bscale[n, k/32] - 127), bscale e8m0 bytes with row stride ldbs >= K/32.
 // 1 <= M <= 16; x / out bf16 or fp16 (DType) with fp32 accumulation. ldx / ldo in elements, ldw in
 // elements of W's storage (16-bit words / bytes); x / w rows 16-B aligned, K a multiple of one 16-byte
-// W load (8 / 16), any N >= 1. Rows >= M, W rows >= N and scale[>= N] are never read.
-enum class SkinnyFormat { W16, E4M3 };
+// W load (8 / 16 / 32), any N >= 1. Rows >= M, W rows >= N, scale[>= N] and bscale rows >= N are never read.
+// (enum class SkinnyFormat { W16, E4M3, MXFP4 }: skinny_format.h)
 struct SkinnyParams {
   const void* x;
   const void* w;
@@ -373,10 +376,13 @@ struct SkinnyParams {
   int64_t ldx, ldw, ldo;
   int M, N, K;
   bool vec_out;        // out rows 8-B aligned: 4 columns per store
-  const float* scale;  // E4M3 only; W16 never reads it
+  const float* scale;  // E4M3 only; the other formats never read it
+  const uint8_t* bscale = nullptr;  // MXFP4 only: block scales and their row stride in bytes
+  int64_t ldbs = 0;
 };
 bool gemm_skinny_ok(SkinnyFormat f, int64_t M, int64_t N, int64_t K, int64_t elem_size);
 void gemm_skinny(const SkinnyParams& p, SkinnyFormat f, DType t, hipStream_t s);
+void gemm_skinny_w4(const SkinnyParams& p, DType t, hipStream_t s);  // the MXFP4 format; gemm_skinny forwards to it
 
 // ---- temperature / top-k sampler (csrc/ops/sample.hip) ----
 // One token per row of logits (B, V; bf16 / fp16 / fp32 (DType), contiguous last dim, any element-aligned
