@@ -61,6 +61,18 @@ ms per token beside the ``graph`` arm of the same run; with ``--sample`` every a
 (all runs are kept, the median is reported).
 
     python -m cs336_systems.bench.decode --sample --no-kernel --arms graph graph+sample graph+fp8 graph+fp8+sample --json profiles/decode_sample.json
+
+Paged cache (``--paged [--page-size 16 64 256]``; ``csrc/flash_attn/fa_decode_paged.hip``): every kernel row also
+times ``ops.decode_attention_paged`` on the same K / V rows held in a page pool, the pages placed by a seeded
+random permutation of a pool with spare pages (a sorted placement would flatter the kernel). The contiguous
+kernel is re-measured in the same run, the arms alternating in five rounds whose samples are pooled: median
+and q20-q80 per arm, the ratio to the contiguous kernel and faster / slower only beyond the spread of both
+sides; ``paged<P>_bitwise`` says whether the paged output has the contiguous kernel's bits (same split
+rule, same rows). The arm ``graph+paged`` is ``generate(..., graph=True, paged=True)`` (page size: the first
+of ``--page-size``, default 64), reported like ``graph`` with the replayed step beside it, and the pages /
+bytes a ``share_prompt`` prefill of the point's prompt holds against the dense cache.
+
+    python -m cs336_systems.bench.decode --paged --no-sweep --arms graph graph+paged --json profiles/decode_paged.json
 """
 
 from __future__ import annotations
@@ -103,8 +115,41 @@ def _kv8_columns(row: dict, base: str, fn, nbytes: float, warmup: int, rep: int)
                           "slower" if row["kv8_us_q20"] > row[f"{base}_us_q80"] else "same")
 
 
+def _paged_pool(k: torch.Tensor, v: torch.Tensor, P: int, seed: int = 0, spare: int = 8):
+    """The (B, H, n, d) rows of ``k`` / ``v`` in ``(num_pages, H, P, d)`` pools with ``spare`` unused pages,
+    the pages placed by a seeded random permutation -> (k_pool, v_pool, block_table)."""
+    B, H, n, d = k.shape
+    T = -(-n // P)
+    num_pages = B * T + spare
+    g = torch.Generator(device=k.device).manual_seed(seed)
+    table = torch.randperm(num_pages, device=k.device, generator=g)[:B * T].view(B, T)
+    pools = []
+    for x in (k, v):
+        if T * P != n:
+            x = torch.nn.functional.pad(x, (0, 0, 0, T * P - n))
+        pool = torch.zeros(num_pages, H, P, d, device=k.device, dtype=k.dtype)
+        pool[table] = x.view(B, H, T, P, d).permute(0, 2, 1, 3, 4)
+        pools.append(pool)
+    return pools[0], pools[1], table.to(torch.int32)
+
+
+def _alternating(fns: dict, warmup: int, rep: int, rounds: int = 5) -> dict:
+    """Time the arms ``fns`` alternating, ``rounds`` times ``rep / rounds`` flushed calls each, and pool each
+    arm's samples -> name -> (median, q20, q80) in us: drift of the box's clocks hits every arm alike."""
+    samples = {name: [] for name in fns}
+    per = max(1, rep // rounds)
+    for r in range(rounds):
+        for name, fn in fns.items():
+            samples[name] += do_bench(fn, warmup=warmup if r == 0 else 2, rep=per, return_all=True)
+    out = {}
+    for name, ts in samples.items():
+        ts = sorted(ts)
+        out[name] = tuple(ts[min(len(ts) - 1, int(round(x * (len(ts) - 1))))] * 1e3 for x in (0.5, 0.2, 0.8))
+    return out
+
+
 def kernel_row(B: int, H: int, d: int, kv_len: int, warmup: int = 10, rep: int = 50, sweep: bool = True,
-               kv_fp8: bool = False) -> dict:
+               kv_fp8: bool = False, paged=()) -> dict:
     dev, dt = "cuda", torch.bfloat16
     torch.manual_seed(0)
     q = torch.randn(B, H, d, device=dev, dtype=dt)
@@ -145,6 +190,25 @@ def kernel_row(B: int, H: int, d: int, kv_len: int, warmup: int = 10, rep: int =
         o8, _ = ops.decode_attention(q, k8, v8, lens, k_scale=ks, v_scale=vs)
         row["kv8_max_abs_diff_vs_bf16"] = (o8.float() - o.float()).abs().max().item()
         del k8, v8, ks, vs
+    if paged:
+        arms = {"contig": lambda: ops.decode_attention(q, k, v, lens)}
+        pools = {}
+        for P in paged:
+            pools[P] = _paged_pool(k, v, P)
+            arms[f"paged{P}"] = lambda P=P: ops.decode_attention_paged(q, *pools[P], lens)
+        stats = _alternating(arms, warmup, rep)
+        for name, (med, lo, hi) in stats.items():
+            row[f"{name}_us"], row[f"{name}_us_q20"], row[f"{name}_us_q80"] = med, lo, hi
+        for P in paged:
+            name = f"paged{P}"
+            row[f"{name}_gbs"] = gbs(row[f"{name}_us"])
+            row[f"{name}_vs_contig"] = row[f"{name}_us"] / row["contig_us"]  # above 1: the paged kernel is slower
+            row[f"{name}_verdict"] = ("faster" if row[f"{name}_us_q80"] < row["contig_us_q20"] else
+                                      "slower" if row[f"{name}_us_q20"] > row["contig_us_q80"] else "same")
+            op, lp = ops.decode_attention_paged(q, *pools[P], lens)
+            oc, lc = ops.decode_attention(q, k, v, lens)
+            row[f"{name}_bitwise"] = bool(torch.equal(op, oc) and torch.equal(lp, lc))
+        del pools, arms
     del q, k, v
     torch.cuda.empty_cache()
     return row
@@ -338,21 +402,28 @@ ARMS = {"cached": dict(use_cache=True), "uncached": dict(use_cache=False), "grap
         "graph+kv8": dict(use_cache=True, graph=True, kv_fp8=True),
         "graph+fp8+kv8": dict(use_cache=True, graph=True, kv_fp8=True),  # (+ weights)
         "graph+sample": dict(use_cache=True, graph=True, sample_on_device=True),
-        "graph+fp8+sample": dict(use_cache=True, graph=True, sample_on_device=True)}  # (+ weights)
-ARM_KEYS = {"graph": "cached_graph", "graph+fp8": "cached_graph_fp8", "graph+fp4": "cached_graph_fp4", "graph+kv8": "cached_graph_kv8",
+        "graph+fp8+sample": dict(use_cache=True, graph=True, sample_on_device=True),  # (+ weights)
+        "graph+paged": dict(use_cache=True, graph=True, paged=True)}  # (+ page_size)
+ARM_KEYS = {"graph": "cached_graph", "graph+paged": "cached_graph_paged", "graph+fp8": "cached_graph_fp8", "graph+fp4": "cached_graph_fp4", "graph+kv8": "cached_graph_kv8",
             "graph+fp8+kv8": "cached_graph_fp8_kv8"}
 
 
-def replay_ms(model, x: torch.Tensor, weights=None, rep: int = 50, kv_fp8: bool = False) -> tuple[float, float, float]:
+def replay_ms(model, x: torch.Tensor, weights=None, rep: int = 50, kv_fp8: bool = False,
+              page_size: int | None = None) -> tuple[float, float, float]:
     """Median, q20 and q80 ms of one replayed decode step on a cache holding the prompt ``x`` (HIP
-    events around the replay; the cache is truncated back after every step)."""
+    events around the replay; the cache is truncated back after every step). ``page_size``: on a
+    ``PagedKVCache``, holding one token more than the prompt, so that the timed step is the ordinary one
+    inside a page and not the one in ``page_size`` that takes a new page."""
     from ..models import DecodeGraph
-    from ..models.kv_cache import KVCache
+    from ..models.kv_cache import KVCache, PagedKVCache
 
     B, prompt = x.shape
-    cache = KVCache(model, B, fp8=kv_fp8)
+    cache = KVCache(model, B, fp8=kv_fp8) if page_size is None else PagedKVCache(model, B, page_size=page_size)
     model.forward_cached(x, cache)
     dg = DecodeGraph(model, cache, capture=True, weights=weights)
+    if page_size is not None:
+        dg.step(x[:, -1:])
+        prompt += 1
     tok, ts = x[:, -1:], []
     for r in range(rep + 5):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -368,7 +439,7 @@ def replay_ms(model, x: torch.Tensor, weights=None, rep: int = 50, kv_fp8: bool 
 
 
 def e2e_row(model_size: str, ctx: int, B: int, prompt: int, new: int, arms=("cached", "uncached", "graph"),
-            runs: int = 1) -> dict:
+            runs: int = 1, page_size: int = 64) -> dict:
     from ..models import build_model
 
     torch.manual_seed(0)
@@ -390,6 +461,9 @@ def e2e_row(model_size: str, ctx: int, B: int, prompt: int, new: int, arms=("cac
             qw = qw or Fp8DecodeWeights(model)
             kw["weights"] = qw
             row["fp8_weight_mbytes"] = qw.nbytes / 2**20
+        if kw.get("paged"):
+            kw["page_size"] = page_size
+            row["page_size"] = page_size
         model.generate(x, 4, top_k=1, **kw)  # warm-up: GEMM selection, allocator
         dts = []
         for _ in range(runs):
@@ -407,8 +481,20 @@ def e2e_row(model_size: str, ctx: int, B: int, prompt: int, new: int, arms=("cac
         row[f"{name}_tok_s"] = B * new / dt
         row[f"{name}_ms_per_step"] = dt / new * 1e3
         if arm in ARM_KEYS:
-            med, lo, hi = replay_ms(model, x, kw.get("weights"), kv_fp8=kw.get("kv_fp8", False))
+            med, lo, hi = replay_ms(model, x, kw.get("weights"), kv_fp8=kw.get("kv_fp8", False),
+                                    page_size=page_size if kw.get("paged") else None)
             row[f"{name}_replay_ms"], row[f"{name}_replay_ms_q20"], row[f"{name}_replay_ms_q80"] = med, lo, hi
+        if kw.get("paged"):  # what a shared prompt holds: one prefill through row 0, forked to the others
+            from ..models.kv_cache import PagedKVCache
+
+            pc = PagedKVCache(model, B, page_size=page_size)
+            model.forward_cached(x[:1], pc.row(0))
+            pc.fork(0)
+            row["shared_prompt_pages_in_use"], row["paged_pool_pages"] = pc.pages_in_use, pc.num_pages
+            row["shared_prompt_mbytes"] = pc.pages_in_use / pc.num_pages * (pc.k.numel() + pc.v.numel()) * 2 / 2**20
+            row["unshared_prompt_pages"] = B * -(-prompt // page_size)
+            row["dense_cache_mbytes"] = 2.0 * len(model.layers) * B * pc.num_heads * ctx * pc.d_head * 2 / 2**20
+            del pc
         if kw.get("kv_fp8") and "kv8_cache_mbytes" not in row:
             from ..models.kv_cache import KVCache
 
@@ -439,7 +525,7 @@ def e2e_row(model_size: str, ctx: int, B: int, prompt: int, new: int, arms=("cac
             if runs > 1:  # faster / slower only when every run of one side beats every run of the other
                 a, b = row[f"{name}_ms_per_step_runs"], row[f"{base}_ms_per_step_runs"]
                 row[f"{name}_verdict"] = "faster" if max(a) < min(b) else "slower" if min(a) > max(b) else "same"
-    for name in ("cached_graph_kv8", "cached_graph_fp8_kv8"):
+    for name in ("cached_graph_kv8", "cached_graph_fp8_kv8", "cached_graph_paged"):
         if "cached_graph_s" in row and f"{name}_s" in row:
             row[f"{name}_speedup_vs_graph"] = row["cached_graph_s"] / row[f"{name}_s"]
             row[f"{name}_replay_vs_graph"] = row[f"{name}_replay_ms"] / row["cached_graph_replay_ms"]
@@ -470,6 +556,11 @@ def main(argv=None):
     ap.add_argument("--sample", action="store_true",
                     help="the fused sampler table (sample_logits against the eager sampling of generate), and three "
                          "timed runs per end-to-end arm")
+    ap.add_argument("--paged", action="store_true",
+                    help="add the paged decode-attention kernel to every kernel row (pages in a seeded random "
+                         "permutation, the contiguous kernel re-measured alternating)")
+    ap.add_argument("--page-size", nargs="+", type=int, default=[16, 64, 256],
+                    help="with --paged: the page sizes of the kernel rows; the first is the graph+paged arm's")
     ap.add_argument("--chunk", action="store_true",
                     help="the multi-token tables: decode_attention_chunk rows instead of the single-token sweep, and "
                          "(with --arms verify) the replayed n-token step; no generate arms")
@@ -512,7 +603,8 @@ def main(argv=None):
             H, d = (int(s) for s in shape.split("x"))
             for B in a.batch:
                 for n in a.kv_len:
-                    r = kernel_row(B, H, d, n, rep=a.rep, sweep=not a.no_sweep, kv_fp8=a.kv_fp8)
+                    r = kernel_row(B, H, d, n, rep=a.rep, sweep=not a.no_sweep, kv_fp8=a.kv_fp8,
+                                   paged=tuple(a.page_size) if a.paged else ())
                     out["kernel"].append(r)
                     print(json.dumps(r), flush=True)
     if a.skinny:
@@ -535,7 +627,8 @@ def main(argv=None):
         if a.kv_fp8:
             points.append((4096, 8, 2048, 512))  # the cache is the larger stream of a step
         for ctx, B, prompt, new in points:
-            r = e2e_row(a.model, ctx, B, prompt, new, arms=a.arms, runs=3 if a.sample else 1)
+            r = e2e_row(a.model, ctx, B, prompt, new, arms=a.arms, runs=3 if a.sample else 1,
+                        page_size=a.page_size[0] if a.paged and len(a.page_size) == 1 else 64)
             out["e2e"].append(r)
             print(json.dumps(r), flush=True)
     if a.json:

@@ -1,6 +1,6 @@
 from .configs import DEFAULT_THETA, DEFAULT_VOCAB, MODEL_CONFIGS, get_model_config, param_count, train_flops_per_token
 from .decode_graph import DecodeGraph, Sampler
-from .kv_cache import KVCache
+from .kv_cache import KVCache, PagedKVCache
 from .quantized import Fp8DecodeWeights, Mxfp4DecodeWeights
 from .speculative import speculative_generate
 from .transformer import (
@@ -37,6 +37,7 @@ __all__ = [
     "Mxfp4DecodeWeights",
     "KVCache",
     "Linear",
+    "PagedKVCache",
     "RMSNorm",
     "RotaryEmbedding",
     "Sampler",

@@ -40,6 +40,12 @@ An FP8 cache (``KVCache(fp8=True)``) needs no argument: the graph is tied to its
 and reads quantized rows (``csrc/flash_attn/fa_decode_kv8.hip``, ``fa_decode_chunk_kv8.hip``) and nothing
 in it synchronizes the host either. ``weights=qw`` and an FP8 cache combine.
 
+A ``PagedKVCache`` needs no argument either: the captured step reads ``cache.block_table`` and
+``cache.lengths`` at their fixed addresses (``csrc/flash_attn/fa_decode_paged.hip``), and ``step`` /
+``advance(n)`` call ``cache.reserve`` for every token they are about to replay -- host-side list work and
+device-side fills, no read-back -- before replaying. ``weights=`` and ``sampler=`` combine with it;
+``tokens > 1`` raises (there is no paged chunk kernel).
+
 ``sampler=Sampler(temperature, top_k, eos_token_id)`` (``tokens == 1`` only) puts the sampling into the
 graph, so that the host neither sees the logits nor issues anything per token but the replay. The
 captured sequence is the model step on ``self.tok``, ``ops.sample_advance`` on its logits
@@ -97,6 +103,9 @@ class DecodeGraph:
             raise ValueError("DecodeGraph needs tokens >= 1")
         if weights is not None and getattr(weights, "model", None) is not model:
             raise ValueError("weights= was built for a different model")
+        self.paged = getattr(cache, "block_table", None) is not None
+        if self.paged and tokens != 1:
+            raise NotImplementedError("DecodeGraph on a PagedKVCache takes tokens == 1: there is no paged chunk step")
         if sampler is not None and tokens != 1:
             raise ValueError("DecodeGraph(sampler=...) samples one token per step: it needs tokens == 1")
         self.model, self.cache, self.n_tokens, self.weights = model, cache, int(tokens), weights
@@ -119,7 +128,9 @@ class DecodeGraph:
         run = self._run_sampled if sampler is not None else lambda: self._run(self.tok)
         # Warm-up and capture leave the cache as they found it: a warm-up step writes its K / V rows
         # from index ``length`` on, which no one reads (past the cache's end the append kernels store nothing),
-        # and lengths / length are put back; capturing executes nothing but the host bookkeeping.
+        # and lengths / length are put back; capturing executes nothing but the host bookkeeping. On a paged
+        # cache nothing is reserved here, so the table and the free list stay as they are: where the slot
+        # has no page the append stores nothing (its guard), else the row lands in the sequence's own page.
         lengths, length = cache.lengths.clone(), cache.length
         self.stream = torch.cuda.Stream(device=dev)
         self.stream.wait_stream(torch.cuda.current_stream(dev))
@@ -201,6 +212,8 @@ class DecodeGraph:
         if cache.length + n > min(cache.max_len, self.model.context_length):
             raise ValueError(f"{cache.length} cached + {n} new tokens exceed the cache "
                              f"(max_len {cache.max_len}, context_length {self.model.context_length})")
+        if self.paged:
+            cache.reserve(int(n))  # pages for every token about to be replayed: host-side, nothing read back
         for _ in range(int(n)):
             if self.graph is None:
                 self._run_sampled()
@@ -239,6 +252,8 @@ class DecodeGraph:
         if cache.length + n > min(cache.max_len, self.model.context_length):
             raise ValueError(f"{cache.length} cached + {n} new token{'s' if n > 1 else ''} exceed the cache "
                              f"(max_len {cache.max_len}, context_length {self.model.context_length})")
+        if self.paged:
+            cache.reserve(n)
         if self.graph is None:
             return self._run(tok)
         self.tok.copy_(tok)

@@ -375,7 +375,7 @@ class CausalMultiHeadSelfAttention(nn.Module):
             return self.output_proj(o)
 
     def forward_cached(self, x3, k_cache, v_cache, start: int, pos=None, kv_len=None, max_kv_len=None,
-                       k_scale=None, v_scale=None) -> torch.Tensor:
+                       k_scale=None, v_scale=None, block_table=None) -> torch.Tensor:
         """Attention of ``forward_cached`` (inference only). ``x3`` (B, n, d_model); ``k_cache`` /
         ``v_cache`` this layer's (B, H, max_len, dk) cache views. ``start == 0``: prefill -- the
         ordinary causal attention over the n tokens at positions 0..n-1, whose rotated K and V are
@@ -386,7 +386,10 @@ class CausalMultiHeadSelfAttention(nn.Module):
         decode kernel's split count (default ``start + n``; a captured step passes a fixed one).
         ``k_scale`` / ``v_scale``: this layer's (B, H, max_len) scale views of an FP8 cache
         (``float8_e4m3fn`` planes): the steps append and read quantized rows, and the prefill, which
-        attends to its own unquantized K / V, stores them through ``ops.kv_quantize_rows``."""
+        attends to its own unquantized K / V, stores them through ``ops.kv_quantize_rows``.
+        ``block_table`` (B, pages per sequence) int32: ``k_cache`` / ``v_cache`` are this layer's
+        (num_pages, H, page_size, dk) pool views of a ``PagedKVCache`` whose pages for the new rows are
+        reserved; the step runs the paged ops and the prefill stores its rows through the table."""
         B, n, _ = x3.shape
         H, dk = self.num_heads, self.d_k
         w = [self.q_proj.weight, self.k_proj.weight, self.v_proj.weight]
@@ -401,7 +404,17 @@ class CausalMultiHeadSelfAttention(nn.Module):
         sc = dict(k_scale=k_scale, v_scale=v_scale) if fp8 else {}
         if not fp8 and qkv.dtype != k_cache.dtype:
             raise ValueError(f"KV cache dtype {k_cache.dtype} does not match the compute dtype {qkv.dtype}")
-        if start > 0 and n > 1:
+        if block_table is not None and start > 0:
+            if n > 1:
+                raise NotImplementedError("a paged KV cache has no chunk step (n > 1 on a non-empty cache)")
+            with annotate("kv_append_rope_paged"):
+                q = ops.kv_append_rope_paged(qkv.view(B, 3 * H * dk), self.positional_encoder.cos,
+                                             self.positional_encoder.sin, pos, k_cache, v_cache, block_table)
+            with annotate("decode_attention_paged"):
+                o, _ = ops.decode_attention_paged(q, k_cache, v_cache, block_table, kv_len,
+                                                  max_kv_len=start + 1 if max_kv_len is None else max_kv_len)
+            o = o.reshape(B, 1, H * dk)
+        elif start > 0 and n > 1:
             with annotate("kv_append_rope_chunk"):
                 q = ops.kv_append_rope_chunk(qkv, self.positional_encoder.cos, self.positional_encoder.sin, pos,
                                              k_cache, v_cache, **sc)
@@ -422,7 +435,15 @@ class CausalMultiHeadSelfAttention(nn.Module):
             with annotate("rope"):
                 q = self.positional_encoder(q, None)
                 k = self.positional_encoder(k, None)
-            if fp8:
+            if block_table is not None:
+                # one index_put_ per plane over (page of row r, :, r % P): no host sync
+                P = k_cache.shape[2]
+                r = torch.arange(n, device=x3.device)
+                pages = block_table[:, r // P].to(torch.int64)  # (B, n)
+                slots = (r % P)[None, :].expand(B, n)
+                k_cache[pages, :, slots] = k.transpose(1, 2).to(k_cache.dtype)  # (B, n, H, dk)
+                v_cache[pages, :, slots] = v.transpose(1, 2).to(v_cache.dtype)
+            elif fp8:
                 with annotate("kv_quantize_rows"):
                     ops.kv_quantize_rows(k, k_cache, k_scale)
                     ops.kv_quantize_rows(v, v_cache, v_scale)
@@ -638,7 +659,12 @@ class BasicsTransformerLM(nn.Module):
         in chunks, the verify step of speculative decoding): per layer the QKV projection of the n
         tokens, ``ops.kv_append_rope_chunk`` and ``ops.decode_attention_chunk``, in which token ``i``
         attends to the cached keys and the chunk's tokens up to itself. ``n == 1`` and the prefill
-        take the same paths whatever ``chunk`` is."""
+        take the same paths whatever ``chunk`` is.
+
+        ``cache`` may be a :class:`~cs336_systems.models.kv_cache.PagedKVCache`: the pages for the new
+        tokens are reserved first (``cache.reserve(n)``; ``RuntimeError`` when the pool is exhausted),
+        the prefill stores its rows through the block table and a step runs ``ops.kv_append_rope_paged``
+        and ``ops.decode_attention_paged``. ``chunk=True`` raises ``NotImplementedError`` on it."""
         if getattr(self, "tensor_parallel", None) is not None or any(
                 layer.attn.context_parallel is not None for layer in self.layers):
             raise NotImplementedError("forward_cached does not support tensor / context parallelism")
@@ -657,6 +683,10 @@ class BasicsTransformerLM(nn.Module):
         if start + n > min(cache.max_len, self.context_length):
             raise ValueError(f"{start} cached + {n} new tokens exceed the cache (max_len {cache.max_len}, "
                              f"context_length {self.context_length})")
+        if getattr(cache, "block_table", None) is not None:
+            if chunk:
+                raise NotImplementedError("forward_cached(chunk=True) is not supported on a PagedKVCache")
+            cache.reserve(n)
         return self._forward_cached(x, cache, start)
 
     def _forward_cached(self, x: torch.Tensor, cache, start: int, max_kv_len: int | None = None) -> torch.Tensor:
@@ -672,8 +702,10 @@ class BasicsTransformerLM(nn.Module):
             kv_len = cache.lengths + n
         ks, vs = getattr(cache, "k_scale", None), getattr(cache, "v_scale", None)
 
-        def scales(i):  # the layer's scale views of an FP8 cache
-            return (None, None) if ks is None else (ks[i], vs[i])
+        table = getattr(cache, "block_table", None)  # a PagedKVCache: cache.k[i] is the layer's page pool
+
+        def scales(i):  # the layer's scale views of an FP8 cache (and the table of a paged one)
+            return (None, None, table) if ks is None else (ks[i], vs[i], table)
         with annotate("embed"):
             h = self.token_embeddings(x)
         n_layers = len(self.layers)
@@ -717,6 +749,9 @@ class BasicsTransformerLM(nn.Module):
         sample_on_device: bool = False,
         generator=None,
         sync_every: int = 16,
+        paged: bool = False,
+        page_size: int = 64,
+        share_prompt: bool = False,
     ) -> torch.Tensor:
         """Autoregressive sampling (``model.py:255-310``) with a working top-k filter (the
         reference's ``masked_fill`` is not in place and its threshold broadcast is wrong for B>1).
@@ -756,8 +791,27 @@ class BasicsTransformerLM(nn.Module):
         ``eos_token_id`` the host polls every ``sync_every`` tokens and stops once every row has ended. At
         B == 1 the result is cut before the first end token, as without this switch; at B > 1 a row that has
         ended keeps emitting ``eos_token_id`` and the result is rectangular, up to and including the column
-        in which the last row ended. ``draft=`` raises: speculation stays greedy."""
+        in which the last row ended. ``draft=`` raises: speculation stays greedy.
+
+        ``paged=True`` (with ``use_cache=True``): the cache is a ``PagedKVCache`` of ``page_size``-row pages
+        with ``max_len = context_length``, filled page by page as the sequences grow. ``share_prompt=True``
+        (with it, or with a ``graph=<DecodeGraph>`` on a paged cache; every row of ``x`` the same prompt, else
+        ``ValueError``): the prompt is prefilled once, through ``cache.row(0)``, and ``cache.fork(0)`` gives
+        the other rows its pages, so B sampled continuations pay one prefill and store the prompt once.
+        ``kv_fp8=True`` and ``draft=`` raise with ``paged=True``; with ``graph=<DecodeGraph>`` the graph's own
+        cache is used, whatever its kind."""
         from .decode_graph import DecodeGraph
+
+        if (paged or share_prompt) and not use_cache:
+            raise ValueError("generate(paged=True / share_prompt=True) needs use_cache=True")
+        if paged and kv_fp8:
+            raise ValueError("generate(paged=True) does not take kv_fp8=True: there is no FP8 paged format")
+        if paged and draft is not None:
+            raise NotImplementedError("generate(paged=True) does not take draft=: a paged cache has no chunk step")
+        if share_prompt and not paged and not isinstance(graph, DecodeGraph):
+            raise ValueError("generate(share_prompt=True) needs paged=True (or a DecodeGraph on a paged cache)")
+        if share_prompt and x.dim() == 2 and not bool((x == x[:1]).all()):
+            raise ValueError("generate(share_prompt=True) needs every row of x to be the same prompt")
 
         if kv_fp8 and not use_cache:
             raise ValueError("generate(kv_fp8=True) needs use_cache=True")
@@ -767,7 +821,7 @@ class BasicsTransformerLM(nn.Module):
             if not use_cache:
                 raise ValueError("generate(sample_on_device=True) needs use_cache=True")
             return self._generate_on_device(x, max_new_tokens, temperature, top_k, eos_token_id, graph, weights, kv_fp8,
-                                            generator, sync_every)
+                                            generator, sync_every, paged, page_size, share_prompt)
         if draft is not None:
             from .speculative import speculative_generate
 
@@ -802,20 +856,17 @@ class BasicsTransformerLM(nn.Module):
             elif not self.lm_head.weight.is_cuda:
                 raise ValueError("generate(graph=True) captures a HIP graph: the model must be on a GPU")
         if use_cache and max_new_tokens > 0:
-            from .kv_cache import KVCache
-
             if dg is not None:
                 cache = dg.cache
                 cache.reset()
             else:
-                w = self.lm_head.weight
-                dev = w.device.type
-                cdt = torch.get_autocast_dtype(dev) if torch.is_autocast_enabled(dev) else w.dtype
-                cache = KVCache(self, x.size(0), device=w.device, dtype=cdt, fp8=kv_fp8)
+                cache = self._new_cache(x.size(0), kv_fp8, paged, page_size)
+            if share_prompt and getattr(cache, "block_table", None) is None:
+                raise ValueError("generate(share_prompt=True) needs a paged cache")
         for _ in range(max_new_tokens):
             ctx = x[:, -self.context_length :] if x.size(1) > self.context_length else x
             if cache is not None and cache.length == 0:
-                logits = self.forward_cached(ctx, cache)  # prefill
+                logits = self._prefill(ctx, cache, share_prompt)
             elif cache is not None and cache.length + 1 == x.size(1) <= self.context_length:
                 if graph is True and dg is None:
                     dg = DecodeGraph(self, cache, capture=True, weights=weights)
@@ -834,11 +885,30 @@ class BasicsTransformerLM(nn.Module):
             x = torch.cat((x, nxt), dim=-1)
         return x[:, orig:]
 
+    def _new_cache(self, batch: int, kv_fp8: bool, paged: bool, page_size: int):
+        """The cache ``generate`` builds for itself: the compute dtype is autocast's if it is on."""
+        from .kv_cache import KVCache, PagedKVCache
+
+        w = self.lm_head.weight
+        dev = w.device.type
+        cdt = torch.get_autocast_dtype(dev) if torch.is_autocast_enabled(dev) else w.dtype
+        if paged:
+            return PagedKVCache(self, batch, page_size=page_size, max_len=self.context_length, device=w.device, dtype=cdt)
+        return KVCache(self, batch, device=w.device, dtype=cdt, fp8=kv_fp8)
+
+    def _prefill(self, ctx, cache, share_prompt: bool) -> torch.Tensor:
+        """The prompt's last-position logits (B, 1, vocab) (all positions without ``share_prompt``). With
+        ``share_prompt`` (a paged cache, equal rows) row 0 alone is prefilled and forked to the others."""
+        if not share_prompt:
+            return self.forward_cached(ctx, cache)
+        logits = self.forward_cached(ctx[:1], cache.row(0))
+        cache.fork(0)
+        return logits[:, -1:].expand(ctx.size(0), -1, -1).contiguous()
+
     def _generate_on_device(self, x, max_new_tokens, temperature, top_k, eos_token_id, graph, weights, kv_fp8,
-                            generator, sync_every) -> torch.Tensor:
+                            generator, sync_every, paged=False, page_size=64, share_prompt=False) -> torch.Tensor:
         """``generate(sample_on_device=True)``: see there."""
         from .decode_graph import DecodeGraph, Sampler
-        from .kv_cache import KVCache
 
         sampler = Sampler(temperature, top_k, eos_token_id)
         if int(sync_every) != sync_every or sync_every < 1:
@@ -871,10 +941,9 @@ class BasicsTransformerLM(nn.Module):
             cache = dg.cache
             cache.reset()
         else:
-            w = self.lm_head.weight
-            dev = w.device.type
-            cdt = torch.get_autocast_dtype(dev) if torch.is_autocast_enabled(dev) else w.dtype
-            cache = KVCache(self, B, device=w.device, dtype=cdt, fp8=kv_fp8)
+            cache = self._new_cache(B, kv_fp8, paged, page_size)
+        if share_prompt and getattr(cache, "block_table", None) is None:
+            raise ValueError("generate(share_prompt=True) needs a paged cache")
         eos = eos_token_id
 
         def pick(logits, s, done):  # token s of every row, (B, 1); a row that has ended stays at eos
@@ -886,7 +955,7 @@ class BasicsTransformerLM(nn.Module):
             return t[:, None], done
 
         # token 0: the prefill on the prompt's last context_length tokens
-        logits = self.forward_cached(x[:, -L:] if P > L else x, cache)
+        logits = self._prefill(x[:, -L:] if P > L else x, cache, share_prompt)
         tok, done = pick(logits, 0, None)
         out = tok
         # cached steps while the sequence fits the window (and the cache)

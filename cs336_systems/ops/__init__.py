@@ -4,7 +4,9 @@ oracle in tests) and a hand-written HIP/CDNA4 kernel (used for GPU tensors)."""
 from ._ext import backend, ext_available, get_backend, load_error, load_ext, set_backend, use_hip
 from .adamw import FusedAdamW, clip_grad_norm_, multi_tensor_l2norm
 from .cross_entropy import cross_entropy, cross_entropy_ref
-from .decode import (decode_attention, decode_attention_chunk, decode_attention_chunk_ref, decode_attention_ref,
+from .decode import (decode_attention, decode_attention_chunk, decode_attention_chunk_ref, decode_attention_paged,
+                     decode_attention_paged_ref, decode_attention_ref, kv_append_rope_paged, kv_append_rope_paged_ref,
+                     paged_gather,
                      kv_append_rope, kv_append_rope_chunk, kv_append_rope_chunk_kv8_ref, kv_append_rope_chunk_ref,
                      kv_append_rope_kv8_ref, kv_append_rope_ref, kv_dequantize, kv_quantize_ref, kv_quantize_rows,
                      kv_quantize_rows_ref)
@@ -39,7 +41,12 @@ __all__ = [
     "decode_attention",
     "decode_attention_chunk",
     "decode_attention_chunk_ref",
+    "decode_attention_paged",
+    "decode_attention_paged_ref",
     "decode_attention_ref",
+    "kv_append_rope_paged",
+    "kv_append_rope_paged_ref",
+    "paged_gather",
     "kv_append_rope",
     "kv_append_rope_chunk",
     "kv_append_rope_chunk_kv8_ref",

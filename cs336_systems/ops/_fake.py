@@ -212,6 +212,19 @@ if hasattr(torch.ops.cs336, "fa_decode_kv8"):  # (absent from libraries built be
         return None
 
 
+if hasattr(torch.ops.cs336, "fa_decode_paged"):  # (absent from libraries built before the paged cache: A/B baselines)
+
+    @register_fake("cs336::fa_decode_paged")
+    def _fa_decode_paged(q, k_pool, v_pool, block_table, kv_len, scale, max_kv_len, splits=0):
+        B, H, D = q.shape
+        return q.new_empty((B, H, D)), q.new_empty((B, H), dtype=torch.float32)
+
+    @register_fake("cs336::kv_append_rope_paged")
+    def _kv_append_rope_paged(qkv, cos, sin, pos, k_pool, v_pool, block_table):
+        _, H, _, D = k_pool.shape
+        return qkv.new_empty((qkv.shape[0], qkv.shape[1], H, D))
+
+
 if hasattr(torch.ops.cs336, "gemm_skinny"):  # (absent from libraries built before the decode graph: A/B baselines)
 
     @register_fake("cs336::gemm_skinny")

@@ -32,6 +32,11 @@ an all-zero row), ``bytes = RNE(clamp(x / scale, -448, 448))`` -- the clamp befo
 quantized from its fp32 rotated value (one rounding, not two through the compute dtype).
 ``kv_quantize_rows`` is the prefill's store of whole (B, H, n, d) K / V tensors. q / o stay bf16,
 fp16 or fp32. An FP8 cache without both scales, or scales with any other cache, raise ``ValueError``.
+
+Paged cache (``csrc/flash_attn/fa_decode_paged.hip``): ``decode_attention_paged`` / ``kv_append_rope_paged``
+take ``(num_pages, H, P, d)`` page pools and an int32 ``block_table`` ``(B, T)`` instead of the dense
+planes: row ``j`` of sequence ``b`` is row ``j % P`` of page ``block_table[b, j // P]``. The references
+gather the rows by the table and apply the dense rules; bf16 / fp16 / fp32 only.
 """
 
 from __future__ import annotations
@@ -326,3 +331,96 @@ def kv_append_rope_chunk(qkv, cos, sin, pos, k_cache, v_cache, *, k_scale=None, 
         return ops().kv_append_rope_chunk(qkv, cos.float().contiguous(), sin.float().contiguous(), pos.contiguous(),
                                           k_cache, v_cache)
     return kv_append_rope_chunk_ref(qkv, cos, sin, pos, k_cache, v_cache)
+
+
+# ---- paged cache (csrc/flash_attn/fa_decode_paged.hip) ----
+_PAGE_SIZES = (16, 32, 64, 128, 256)
+
+
+def paged_gather(pool, block_table):
+    """The sequences' rows as a dense ``(B, H, T * P, d)`` tensor: ``pool`` ``(num_pages, H, P, d)``
+    read through ``block_table`` ``(B, T)``. An entry outside ``[0, num_pages)`` reads some page of the
+    pool (callers mask those rows by the length)."""
+    NP, H, P, d = pool.shape
+    B, T = block_table.shape
+    g = pool[block_table.to(torch.int64).clamp(0, NP - 1)]  # (B, T, H, P, d)
+    return g.permute(0, 2, 1, 3, 4).reshape(B, H, T * P, d)
+
+
+def decode_attention_paged_ref(q, k_pool, v_pool, block_table, kv_len, scale=None):
+    """:func:`decode_attention_ref` on the rows gathered by the table."""
+    return decode_attention_ref(q, paged_gather(k_pool, block_table), paged_gather(v_pool, block_table), kv_len, scale)
+
+
+def kv_append_rope_paged_ref(qkv, cos, sin, pos, k_pool, v_pool, block_table):
+    """The rule of :func:`kv_append_rope_chunk_ref` with the slot looked up in the table: token ``i`` of
+    sequence ``b`` is rotated at ``pos[b] + i`` and stored in row ``slot % P`` of page
+    ``block_table[b, slot // P]``; a slot outside ``[0, min(T * P, ctx))`` or an entry outside
+    ``[0, num_pages)`` stores nothing and zeroes the token's q. (The mask indexing reads back: this is the
+    reference.)"""
+    two_d = qkv.dim() == 2
+    if two_d:
+        qkv = qkv[:, None]
+    NP, H, P, d = k_pool.shape
+    B, n = qkv.shape[:2]
+    T = block_table.shape[1]
+    q, k, v = (t.transpose(1, 2) for t in qkv.reshape(B, n, 3, H, d).unbind(2))  # (B, H, n, d)
+    lim = min(T * P, cos.shape[0])
+    slot = pos.to(torch.int64)[:, None] + torch.arange(n, device=qkv.device)[None, :]  # (B, n)
+    p = slot.clamp(0, lim - 1)
+    page = block_table.to(torch.int64).gather(1, p // P)
+    ok = (slot >= 0) & (slot < lim) & (page >= 0) & (page < NP)
+    q_rot = rope_ref(q, cos, sin, p[:, None, :])
+    k_rot = rope_ref(k, cos, sin, p[:, None, :])
+    k_pool[page[ok], :, (p % P)[ok]] = k_rot.transpose(1, 2)[ok].to(k_pool.dtype)  # (tokens, H, d)
+    v_pool[page[ok], :, (p % P)[ok]] = v.transpose(1, 2)[ok].to(v_pool.dtype)
+    q_rot = torch.where(ok[:, None, :, None], q_rot, torch.zeros_like(q_rot)).transpose(1, 2).contiguous()
+    return q_rot[:, 0] if two_d else q_rot  # (B, (n,) H, d)
+
+
+def _paged_layout_ok(k_pool, v_pool, block_table) -> bool:
+    return (_cache_layout_ok(k_pool) and _cache_layout_ok(v_pool) and k_pool.shape == v_pool.shape
+            and k_pool.shape[2] in _PAGE_SIZES and block_table.dim() == 2 and block_table.stride(-1) == 1)
+
+
+def decode_attention_paged(q, k_pool, v_pool, block_table, kv_len, scale=None, max_kv_len=None, splits=0):
+    """:func:`decode_attention` on a paged cache: ``k_pool`` / ``v_pool`` ``(num_pages, H, P, d)`` views
+    (``P`` in 16 ... 256; any page / head strides), ``block_table`` ``(B, T)`` int32 on the device, row
+    ``j`` of sequence ``b`` being row ``j % P`` of page ``block_table[b, j // P]``. The table is read up
+    to entry ``(kv_len[b] - 1) // P`` only; later entries may hold ``-1`` or stale ids. The result is a
+    function of the logical rows: any placement of the pages gives the same bits. ``max_kv_len``
+    (default ``T * P``) and ``splits`` as in :func:`decode_attention`."""
+    d = q.shape[-1]
+    scale = 1.0 / math.sqrt(d) if scale is None else float(scale)
+    if (use_hip(q, k_pool, v_pool) and d in _DECODE_D and q.dtype in (torch.bfloat16, torch.float16, torch.float32)
+            and _paged_layout_ok(k_pool, v_pool, block_table)):
+        max_len = block_table.shape[1] * k_pool.shape[2]
+        bound = max_len if max_kv_len is None else min(int(max_kv_len), max_len)
+        if kv_len.dtype != torch.int32:
+            kv_len = kv_len.to(torch.int32)
+        if block_table.dtype != torch.int32:
+            block_table = block_table.to(torch.int32)
+        return ops().fa_decode_paged(q, k_pool, v_pool, block_table, kv_len.contiguous(), scale, bound, int(splits))
+    return decode_attention_paged_ref(q, k_pool, v_pool, block_table, kv_len, scale)
+
+
+def kv_append_rope_paged(qkv, cos, sin, pos, k_pool, v_pool, block_table):
+    """``qkv`` ``(B, 3*H*d)`` (one token, the decode step) or ``(B, n, 3*H*d)`` -> rotated q ``(B, H, d)``
+    / ``(B, n, H, d)``; rotated k and plain v are written through the table (see
+    :func:`kv_append_rope_paged_ref` for what is not stored)."""
+    d = k_pool.shape[-1]
+    es = qkv.element_size()
+    q3 = qkv[:, None] if qkv.dim() == 2 else qkv
+    if (use_hip(qkv, k_pool, v_pool) and d in _DECODE_D
+            and qkv.dtype in (torch.bfloat16, torch.float16, torch.float32) and q3.dim() == 3 and q3.shape[1] >= 1
+            and q3.stride(-1) == 1 and q3.data_ptr() % 16 == 0
+            and (q3.stride(0) * es) % 16 == 0 and (q3.stride(1) * es) % 16 == 0
+            and _paged_layout_ok(k_pool, v_pool, block_table)):
+        if pos.dtype != torch.int32:
+            pos = pos.to(torch.int32)
+        if block_table.dtype != torch.int32:
+            block_table = block_table.to(torch.int32)
+        out = ops().kv_append_rope_paged(q3, cos.float().contiguous(), sin.float().contiguous(), pos.contiguous(),
+                                         k_pool, v_pool, block_table)
+        return out[:, 0] if qkv.dim() == 2 else out
+    return kv_append_rope_paged_ref(qkv, cos, sin, pos, k_pool, v_pool, block_table)

@@ -1592,6 +1592,139 @@ at::Tensor kv_append_rope_chunk(const at::Tensor& qkv, const at::Tensor& cos, co
   return q_out;
 }
 
+// ------------------------------------------------------------------------------------------
+// Paged KV cache: decode attention / append through a block table (csrc/flash_attn/fa_decode_paged.hip)
+// ------------------------------------------------------------------------------------------
+// (num_pages, H, P, D) pool view, P a power of two in [16, 256]: check_cache's layout rules (any
+// page / head strides), and the (B, max_len / P) int32 table. Returns log2 P.
+int check_paged(const at::Tensor& k_pool, const at::Tensor& v_pool, const at::Tensor& table, int64_t B,
+                const char* op) {
+  check_cache(k_pool, "k_pool");
+  check_cache(v_pool, "v_pool");
+  TORCH_CHECK(k_pool.sizes() == v_pool.sizes(), "cs336: k_pool / v_pool shape mismatch");
+  const int64_t P = k_pool.size(2);
+  TORCH_CHECK(P == 16 || P == 32 || P == 64 || P == 128 || P == 256, "cs336: ", op,
+              " page size must be 16, 32, 64, 128 or 256 (got ", P, ")");
+  TORCH_CHECK(k_pool.size(0) >= 1 && k_pool.size(0) < ((int64_t)1 << 31), "cs336: ", op,
+              " needs 1 <= num_pages < 2^31");
+  TORCH_CHECK(table.is_cuda() && table.scalar_type() == at::kInt && table.dim() == 2 && table.size(0) == B &&
+                  table.stride(1) == 1 && table.stride(0) >= 0,
+              "cs336: block_table must be an int32 (B, pages per sequence) device tensor with a contiguous last dim");
+  TORCH_CHECK(table.size(1) * P < ((int64_t)1 << 30), "cs336: ", op, " max_len (table columns * page size) too large");
+  int lg = 4;
+  while (((int64_t)1 << lg) < P) ++lg;
+  return lg;
+}
+
+std::tuple<at::Tensor, at::Tensor> fa_decode_paged(const at::Tensor& q, const at::Tensor& k_pool,
+                                                   const at::Tensor& v_pool, const at::Tensor& table,
+                                                   const at::Tensor& kv_len, double scale, int64_t max_kv_len,
+                                                   int64_t splits) {
+  check_cuda(q, "q");
+  TORCH_CHECK(q.dim() == 3, "cs336: fa_decode_paged q must be (B, H, D)");
+  const int64_t B = q.size(0), H = q.size(1), D = q.size(2);
+  TORCH_CHECK(D == 32 || D == 64 || D == 80 || D == 128,
+              "cs336: fa_decode_paged head dim must be 32, 64, 80 or 128 (got ", D, ")");
+  const int lg = check_paged(k_pool, v_pool, table, B, "fa_decode_paged");
+  const int64_t max_len = table.size(1) << lg;
+  TORCH_CHECK(q.scalar_type() == k_pool.scalar_type() && q.scalar_type() == v_pool.scalar_type(),
+              "cs336: q / k_pool / v_pool dtype mismatch");
+  TORCH_CHECK(k_pool.size(1) == H && k_pool.size(3) == D, "cs336: pools must be (num_pages, H, P, D) matching q");
+  TORCH_CHECK(k_pool.device() == q.device() && v_pool.device() == q.device() && kv_len.device() == q.device() &&
+                  table.device() == q.device(),
+              "cs336: fa_decode_paged tensors must be on one device");
+  TORCH_CHECK(kv_len.scalar_type() == at::kInt && kv_len.dim() == 1 && kv_len.size(0) == B && kv_len.is_contiguous(),
+              "cs336: kv_len must be a contiguous int32 (B,) device tensor");
+  TORCH_CHECK(max_kv_len >= 0 && max_kv_len <= max_len,
+              "cs336: max_kv_len must be in [0, block_table.shape[1] * page_size]");
+  TORCH_CHECK(splits >= 0 && splits <= 64, "cs336: splits must be in [0, 64] (0 = choose)");
+  TORCH_CHECK(B * H * 64 < ((int64_t)1 << 31), "cs336: fa_decode_paged grid too large");
+  const DType t = to_dtype(q);
+  c10::DeviceGuard g(q.device());
+  const at::Tensor qc = q.contiguous();
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(qc.data_ptr()) % 16) == 0, "cs336: q must be 16-byte aligned");
+  at::Tensor o = at::empty({B, H, D}, q.options());
+  at::Tensor lse = at::empty({B, H}, q.options().dtype(at::kFloat));
+  if (B * H == 0) return {o, lse};
+  cs336::DecodePagedParams p;
+  p.q = qc.data_ptr();
+  p.k = k_pool.data_ptr();
+  p.v = v_pool.data_ptr();
+  p.o = o.data_ptr();
+  p.lse = lse.data_ptr<float>();
+  p.kv_len = kv_len.data_ptr<int>();
+  p.table = table.data_ptr<int>();
+  p.table_sb = table.stride(0);
+  p.k_sp = k_pool.stride(0); p.k_sh = k_pool.stride(1); p.k_sn = k_pool.stride(2);
+  p.v_sp = v_pool.stride(0); p.v_sh = v_pool.stride(1); p.v_sn = v_pool.stride(2);
+  p.B = (int)B; p.H = (int)H; p.D = (int)D; p.max_len = (int)max_len;
+  p.num_pages = (int)k_pool.size(0); p.lg_page = lg;
+  p.scale = (float)scale;
+  p.splits = splits > 0 ? (int)splits : cs336::fa_decode_splits((int)B, (int)H, (int)D, t, (int)max_kv_len);
+  at::Tensor ws;
+  if (p.splits > 1) {
+    ws = at::empty({(int64_t)p.splits * B * H * (D + 1)}, q.options().dtype(at::kFloat));
+    p.opart = ws.data_ptr<float>();
+    p.lpart = p.opart + (int64_t)p.splits * B * H * D;
+  }
+  cs336::fa_decode_paged(p, t, stream());
+  return {o, lse};
+}
+
+// qkv (B, n, 3*H*D) -> rotated q (B, n, H, D); the Python wrapper gives a (B, 3*H*D) call n == 1
+at::Tensor kv_append_rope_paged(const at::Tensor& qkv, const at::Tensor& cos, const at::Tensor& sin,
+                                const at::Tensor& pos, at::Tensor& k_pool, at::Tensor& v_pool,
+                                const at::Tensor& table) {
+  check_cuda(qkv, "qkv");
+  TORCH_CHECK(qkv.dim() == 3 && qkv.stride(2) == 1, "cs336: qkv must be (B, n, 3*H*D) with a contiguous last dim");
+  const int64_t B = qkv.size(0), n = qkv.size(1);
+  const int lg = check_paged(k_pool, v_pool, table, B, "kv_append_rope_paged");
+  const int64_t H = k_pool.size(1), D = k_pool.size(3), max_len = table.size(1) << lg;
+  TORCH_CHECK(qkv.size(2) == 3 * H * D, "cs336: qkv must be (B, n, 3*H*D) for (num_pages, H, P, D) pools");
+  TORCH_CHECK(D == 32 || D == 64 || D == 80 || D == 128,
+              "cs336: kv_append_rope_paged head dim must be 32, 64, 80 or 128 (got ", D, ")");
+  TORCH_CHECK(qkv.scalar_type() == k_pool.scalar_type() && qkv.scalar_type() == v_pool.scalar_type(),
+              "cs336: qkv / k_pool / v_pool dtype mismatch");
+  const int64_t es = qkv.element_size();
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16) == 0 && (qkv.stride(0) * es) % 16 == 0 &&
+                  (qkv.stride(1) * es) % 16 == 0 && qkv.stride(0) >= 0 && qkv.stride(1) >= 0,
+              "cs336: qkv rows must be 16-byte aligned");
+  TORCH_CHECK(cos.is_cuda() && sin.is_cuda() && cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat &&
+                  cos.dim() == 2 && cos.is_contiguous() && sin.is_contiguous() && cos.sizes() == sin.sizes() &&
+                  cos.size(1) * 2 == D,
+              "cs336: rope cache must be contiguous fp32 (ctx, D/2)");
+  TORCH_CHECK(pos.scalar_type() == at::kInt && pos.dim() == 1 && pos.size(0) == B && pos.is_contiguous(),
+              "cs336: pos must be a contiguous int32 (B,) device tensor");
+  TORCH_CHECK(pos.device() == qkv.device() && cos.device() == qkv.device() && sin.device() == qkv.device() &&
+                  k_pool.device() == qkv.device() && v_pool.device() == qkv.device() && table.device() == qkv.device(),
+              "cs336: kv_append_rope_paged tensors must be on one device");
+  TORCH_CHECK(n < ((int64_t)1 << 31) && B * 3 * H * (D / 8) < ((int64_t)1 << 31) &&
+                  B * n < ((int64_t)1 << 31) / (3 * H * (D / 8) > 0 ? 3 * H * (D / 8) : 1) &&
+                  cos.size(0) < ((int64_t)1 << 31),
+              "cs336: kv_append_rope_paged too large for 32-bit indexing");
+  c10::DeviceGuard g(qkv.device());
+  at::Tensor q_out = at::empty({B, n, H, D}, qkv.options());
+  if (B * H * n == 0) return q_out;
+  cs336::AppendPagedParams p;
+  p.qkv = qkv.data_ptr();
+  p.qkv_sb = qkv.stride(0);
+  p.qkv_sn = qkv.stride(1);
+  p.cos = cos.data_ptr<float>();
+  p.sin = sin.data_ptr<float>();
+  p.pos = pos.data_ptr<int>();
+  p.table = table.data_ptr<int>();
+  p.table_sb = table.stride(0);
+  p.q_out = q_out.data_ptr();
+  p.k = k_pool.data_ptr();
+  p.v = v_pool.data_ptr();
+  p.k_sp = k_pool.stride(0); p.k_sh = k_pool.stride(1); p.k_sn = k_pool.stride(2);
+  p.v_sp = v_pool.stride(0); p.v_sh = v_pool.stride(1); p.v_sn = v_pool.stride(2);
+  p.B = (int)B; p.n = (int)n; p.H = (int)H; p.D = (int)D; p.max_len = (int)max_len; p.ctx = (int)cos.size(0);
+  p.num_pages = (int)k_pool.size(0); p.lg_page = lg;
+  cs336::kv_append_rope_paged(p, to_dtype(qkv), stream());
+  return q_out;
+}
+
 // the query tile fa_decode_chunk picks for n (benchmarks and profiles report it)
 int64_t fa_decode_chunk_qt(int64_t n) { return cs336::fa_decode_chunk_qt((int)std::min<int64_t>(n, 1 << 20)); }
 
@@ -2046,6 +2179,12 @@ TORCH_LIBRARY(cs336, m) {
   m.def("fa_decode_kv8_key_tile(int D, int n) -> int", &fa_decode_kv8_key_tile);
   m.def("fa_decode_kv8_splits(int B, int H, int D, int n, int max_kv_len) -> int", &fa_decode_kv8_splits);
   m.def(
+      "fa_decode_paged(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor kv_len, float scale, "
+      "int max_kv_len, int splits=0) -> (Tensor, Tensor)");
+  m.def(
+      "kv_append_rope_paged(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor(a!) k_pool, Tensor(b!) v_pool, "
+      "Tensor block_table) -> Tensor");
+  m.def(
       "fa_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale, Tensor? rope_cos=None, Tensor? rope_sin=None, "
       "Tensor? rope_pos=None) -> (Tensor, Tensor)");
   m.def(
@@ -2119,6 +2258,8 @@ TORCH_LIBRARY_IMPL(cs336, CUDA, m) {
   m.impl("fa_decode_chunk_kv8", &fa_decode_chunk_kv8);
   m.impl("kv_append_rope_kv8", &kv_append_rope_kv8);
   m.impl("kv_append_rope_chunk_kv8", &kv_append_rope_chunk_kv8);
+  m.impl("fa_decode_paged", &fa_decode_paged);
+  m.impl("kv_append_rope_paged", &kv_append_rope_paged);
   m.impl("kv_quantize_rows", &kv_quantize_rows);
   m.impl("fa_fwd", &fa_fwd);
   m.impl("fa_fwd_ot", &fa_fwd_ot);

@@ -311,6 +311,51 @@ void kv_append_rope_chunk(const AppendChunkParams& p, DType t, hipStream_t s);
 void fa_decode_merge(const DecodeParams& p, DType t, hipStream_t s);
 void fa_decode_chunk_merge(const DecodeChunkParams& p, DType t, hipStream_t s);
 
+// ---- paged KV cache (csrc/flash_attn/fa_decode_paged.hip) ----
+// fa_decode / kv_append_rope_chunk on a page pool: k / v are (num_pages, H, P, D) views (page, head and
+// row strides below; last dim contiguous, 16-B rows), P = 1 << lg_page, and row j of sequence b is
+// row j & (P - 1) of page table[b, j >> lg_page]. max_len = table columns * P.
+struct DecodePagedParams {
+  const void* q;  // (B, H, D) contiguous
+  const void* k;
+  const void* v;
+  void* o;            // (B, H, D) contiguous, q's dtype
+  float* lse;         // (B, H) natural-log LSE
+  const int* kv_len;  // (B,) device; clamped to [0, max_len] in the kernel
+  const int* table;   // (B, max_len / P) device, row stride table_sb; read up to entry (kv_len[b] - 1) >> lg_page
+  int64_t table_sb;
+  int64_t k_sp, k_sh, k_sn;
+  int64_t v_sp, v_sh, v_sn;
+  int B, H, D, max_len, num_pages, lg_page;
+  float scale;
+  // splits > 1: fp32 partials in fa_decode's layout, merged by fa_decode_merge
+  int splits = 1;
+  float* opart = nullptr;
+  float* lpart = nullptr;
+};
+// (split count and key tile: fa_decode_splits / fa_decode_key_tile)
+void fa_decode_paged(const DecodePagedParams& p, DType t, hipStream_t s);
+
+// n >= 1 tokens per sequence, as AppendChunkParams; token i goes to slot pos[b] + i through the table.
+// Nothing is stored (q_out row zeroed) for a slot outside [0, min(max_len, ctx)) or a table entry
+// outside [0, num_pages).
+struct AppendPagedParams {
+  const void* qkv;
+  int64_t qkv_sb, qkv_sn;  // batch and token strides (elements)
+  const float* cos;        // (ctx, D/2) fp32
+  const float* sin;
+  const int* pos;  // (B,) device: slot of the first token
+  const int* table;
+  int64_t table_sb;
+  void* q_out;
+  void* k;
+  void* v;
+  int64_t k_sp, k_sh, k_sn;
+  int64_t v_sp, v_sh, v_sn;
+  int B, n, H, D, max_len, ctx, num_pages, lg_page;
+};
+void kv_append_rope_paged(const AppendPagedParams& p, DType t, hipStream_t s);
+
 // ---- FP8 KV cache (csrc/flash_attn/fa_decode_kv8.hip, fa_decode_chunk_kv8.hip) ----
 // A cached row is D OCP e4m3 bytes and one fp32 scale, row = bytes * scale: k / v of the structs are
 // (B, H, max_len, D) byte planes (strides in bytes, rows 16-B aligned, row stride below 2^22) and k_scale / v_scale
