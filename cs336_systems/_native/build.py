@@ -34,6 +34,7 @@ ARCH = os.environ.get("CS336_OFFLOAD_ARCH", os.environ.get("PYTORCH_ROCM_ARCH", 
 
 
 VGPR_FORM = ("-mllvm", "-amdgpu-mfma-vgpr-form")
+NO_PACKED_F32 = ("-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")
 
 
 def _torch_paths():
@@ -109,6 +110,9 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False, s
             # and is slower than two single ops beside MFMAs (MI355X_MICROARCH.md, filler prices)
             if "cs336-build: no-slp" in head:
                 flags = flags + ["-fno-slp-vectorize"]
+            # ... and keep the backend from selecting v_pk_{add,mul,fma}_f32 at all
+            if "cs336-build: no-packed-f32" in head:
+                flags = flags + list(NO_PACKED_F32)
             jobs_list.append([hipcc, *flags, "-c", src, "-o", obj])
     for src in host:
         obj = _obj_for(src)

@@ -73,6 +73,16 @@ of ``--page-size``, default 64), reported like ``graph`` with the replayed step 
 bytes a ``share_prompt`` prefill of the point's prompt holds against the dense cache.
 
     python -m cs336_systems.bench.decode --paged --no-sweep --arms graph graph+paged --json profiles/decode_paged.json
+
+Extend attention (``--extend``; ``csrc/flash_attn/fa_extend.hip``): n in 16 / 64 / 256 / 1024 new queries on
+512 / 4096 / 16384 keys (n <= keys), B 1 and 8: ``ops.extend_attention`` and ``ops.extend_attention_paged`` (page
+size 64, pages in a seeded random permutation) against ``ops.decode_attention_chunk``, the three alternating in
+one run, with the spread rule, the achieved TFLOP/s and GB/s of the algorithm's operations and bytes, and whether
+the paged output has the dense kernel's bits. Then the xl prefill of a 2048-token prompt at B 1 in one shot and
+with ``prefill_chunk`` 256 and 512: wall-clock ms and the peak of ``torch.cuda.max_memory_allocated`` above the
+weights and the cache.
+
+    python -m cs336_systems.bench.decode --extend --json profiles/decode_extend.json
 """
 
 from __future__ import annotations
@@ -255,6 +265,80 @@ def chunk_row(B: int, H: int, d: int, kv_len: int, n: int, warmup: int = 10, rep
     del q, k, v
     torch.cuda.empty_cache()
     return row
+
+
+EXTEND_N = (16, 64, 256, 1024)
+
+
+def extend_row(B: int, H: int, d: int, kv_len: int, n: int, warmup: int = 5, rep: int = 50, page_size: int = 64) -> dict:
+    """``ops.extend_attention`` and its paged sibling (pages in a seeded random permutation) beside
+    ``ops.decode_attention_chunk``, what the parent commit runs for the same job, the three arms alternating:
+    median and q20-q80 in us, faster / slower only beyond the spread of both sides. FLOPs and bytes are the
+    algorithm's: 4 d per (query, visible key) pair, K / V rows, q and o once."""
+    dev, dt = "cuda", torch.bfloat16
+    torch.manual_seed(0)
+    q = torch.randn(B, n, H, d, device=dev, dtype=dt)
+    k = torch.randn(B, H, kv_len, d, device=dev, dtype=dt)
+    v = torch.randn(B, H, kv_len, d, device=dev, dtype=dt)
+    lens = torch.full((B,), kv_len, dtype=torch.int32, device=dev)
+    pool = _paged_pool(k, v, page_size)
+    flops = 4.0 * d * B * H * (n * kv_len - n * (n - 1) / 2)
+    nbytes = 2.0 * B * H * d * (kv_len + n) * k.element_size()
+    row = dict(B=B, H=H, d=d, kv_len=kv_len, n=n, dtype="bf16", page_size=page_size, gflop=flops / 1e9,
+               mbytes=nbytes / 2**20, splits=int(torch.ops.cs336.fa_extend_splits(B, H, n, kv_len)),
+               chunk_query_tile=int(torch.ops.cs336.fa_decode_chunk_qt(n)))
+    arms = {"chunk": lambda: ops.decode_attention_chunk(q, k, v, lens),
+            "extend": lambda: ops.extend_attention(q, k, v, lens),
+            "extend_paged": lambda: ops.extend_attention_paged(q, *pool, lens)}
+    for name, (med, lo, hi) in _alternating(arms, warmup, rep).items():
+        row[f"{name}_us"], row[f"{name}_us_q20"], row[f"{name}_us_q80"] = med, lo, hi
+    for name in ("extend", "extend_paged"):
+        row[f"{name}_tflops"] = flops / (row[f"{name}_us"] * 1e-6) / 1e12
+        row[f"{name}_gbs"] = nbytes / (row[f"{name}_us"] * 1e-6) / 1e9
+        row[f"{name}_vs_chunk"] = row[f"{name}_us"] / row["chunk_us"]  # below 1: the extend kernel is faster
+        row[f"{name}_verdict"] = ("faster" if row[f"{name}_us_q80"] < row["chunk_us_q20"] else
+                                  "slower" if row[f"{name}_us_q20"] > row["chunk_us_q80"] else "same")
+    oc, _ = ops.decode_attention_chunk(q, k, v, lens)
+    oe, le = ops.extend_attention(q, k, v, lens)
+    op, lp = ops.extend_attention_paged(q, *pool, lens)
+    row["max_abs_diff_vs_chunk"] = (oe.float() - oc.float()).abs().max().item()
+    row["paged_bitwise"] = bool(torch.equal(op, oe) and torch.equal(lp, le))
+    del q, k, v, pool
+    torch.cuda.empty_cache()
+    return row
+
+
+def extend_prefill_rows(model_size: str, prompt: int = 2048, chunks=(None, 256, 512), runs: int = 5) -> list[dict]:
+    """Prefill of a ``prompt``-token prompt at B 1: one shot, and in pieces through ``extend_cached``. Median /
+    min / max wall-clock ms over ``runs`` (after one warm-up) and the peak of ``torch.cuda.max_memory_allocated``
+    above the bytes held before the call (weights and cache)."""
+    from ..models import build_model
+    from ..models.kv_cache import KVCache
+
+    torch.manual_seed(0)
+    model = build_model(model_size, prompt, device="cuda").to(torch.bfloat16).eval()
+    x = torch.randint(0, model.vocab_size, (1, prompt), device="cuda")
+    cache = KVCache(model, 1)
+    rows, ref = [], None
+    for chunk in chunks:
+        ts = []
+        for r in range(runs + 1):
+            cache.reset()
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            held = torch.cuda.memory_allocated()
+            t0 = time.perf_counter()
+            logits = model._prefill(x, cache, False, chunk)[:, -1]
+            torch.cuda.synchronize()
+            if r:
+                ts.append((time.perf_counter() - t0) * 1e3)
+            peak = torch.cuda.max_memory_allocated() - held
+        ts.sort()
+        ref = logits.float() if ref is None else ref
+        rows.append(dict(model=model_size, B=1, prompt=prompt, prefill_chunk=chunk, dtype="bf16", ms=ts[len(ts) // 2],
+                         ms_min=ts[0], ms_max=ts[-1], peak_activation_mbytes=peak / 2**20,
+                         last_logits_max_abs_diff_vs_one_shot=(logits.float() - ref).abs().max().item()))
+    return rows
 
 
 def verify_rows(model_size: str, ctx: int = 512, B: int = 1, prefix: int = 256, rep: int = 50) -> list[dict]:
@@ -564,14 +648,41 @@ def main(argv=None):
     ap.add_argument("--chunk", action="store_true",
                     help="the multi-token tables: decode_attention_chunk rows instead of the single-token sweep, and "
                          "(with --arms verify) the replayed n-token step; no generate arms")
+    ap.add_argument("--extend", action="store_true",
+                    help="the extend-attention table (extend_attention and its paged sibling against "
+                         "decode_attention_chunk; batch default 1 8) and the xl prefill of 2048 tokens in one shot and "
+                         "in pieces; no generate arms")
     ap.add_argument("--arms", nargs="+", default=["cached", "uncached", "graph"], choices=sorted(ARMS) + ["verify"])
     ap.add_argument("--json", default=None)
     a = ap.parse_args(argv)
+    if a.extend and a.batch == [1, 8, 64]:
+        a.batch = [1, 8]
     if not torch.cuda.is_available():
         raise SystemExit("bench.decode needs a GPU")
     if not ops.load_ext():
         raise SystemExit(ops.load_error())
     out = dict(hbm_achievable_gbs=HBM_ACHIEVABLE_GBS, kernel=[], skinny=[], e2e=[])
+    if a.extend:
+        out.update(extend=[], extend_prefill=[])
+        if not a.no_kernel:
+            for shape in a.shapes:
+                H, d = (int(s) for s in shape.split("x"))
+                for B in a.batch:
+                    for kv in a.kv_len:
+                        for n in EXTEND_N:
+                            if n > kv:  # (kv_len counts the chunk's own rows)
+                                continue
+                            r = extend_row(B, H, d, kv, n, rep=a.rep)
+                            out["extend"].append(r)
+                            print(json.dumps(r), flush=True)
+        if not a.no_e2e:
+            for r in extend_prefill_rows(a.model):
+                out["extend_prefill"].append(r)
+                print(json.dumps(r), flush=True)
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return out
     if a.chunk:
         from ..utils.gpu_monitor import GpuSampler
 

@@ -375,7 +375,7 @@ class CausalMultiHeadSelfAttention(nn.Module):
             return self.output_proj(o)
 
     def forward_cached(self, x3, k_cache, v_cache, start: int, pos=None, kv_len=None, max_kv_len=None,
-                       k_scale=None, v_scale=None, block_table=None) -> torch.Tensor:
+                       k_scale=None, v_scale=None, block_table=None, *, extend: bool = False) -> torch.Tensor:
         """Attention of ``forward_cached`` (inference only). ``x3`` (B, n, d_model); ``k_cache`` /
         ``v_cache`` this layer's (B, H, max_len, dk) cache views. ``start == 0``: prefill -- the
         ordinary causal attention over the n tokens at positions 0..n-1, whose rotated K and V are
@@ -389,7 +389,10 @@ class CausalMultiHeadSelfAttention(nn.Module):
         attends to its own unquantized K / V, stores them through ``ops.kv_quantize_rows``.
         ``block_table`` (B, pages per sequence) int32: ``k_cache`` / ``v_cache`` are this layer's
         (num_pages, H, page_size, dk) pool views of a ``PagedKVCache`` whose pages for the new rows are
-        reserved; the step runs the paged ops and the prefill stores its rows through the table."""
+        reserved; the step runs the paged ops and the prefill stores its rows through the table.
+        ``extend=True`` (16-bit or fp32 caches): a step of n > 1 tokens runs the chunk append (dense or
+        paged) and then ``ops.extend_attention`` / ``ops.extend_attention_paged``, the MFMA kernel, instead
+        of the chunk kernel; it is how a paged cache takes n > 1 tokens at all."""
         B, n, _ = x3.shape
         H, dk = self.num_heads, self.d_k
         w = [self.q_proj.weight, self.k_proj.weight, self.v_proj.weight]
@@ -404,7 +407,23 @@ class CausalMultiHeadSelfAttention(nn.Module):
         sc = dict(k_scale=k_scale, v_scale=v_scale) if fp8 else {}
         if not fp8 and qkv.dtype != k_cache.dtype:
             raise ValueError(f"KV cache dtype {k_cache.dtype} does not match the compute dtype {qkv.dtype}")
-        if block_table is not None and start > 0:
+        if extend and start > 0 and n > 1:
+            if fp8:
+                raise NotImplementedError("the extend step has no FP8 cache format")
+            mk = start + n if max_kv_len is None else max_kv_len
+            cos, sin = self.positional_encoder.cos, self.positional_encoder.sin
+            if block_table is not None:
+                with annotate("kv_append_rope_paged"):
+                    q = ops.kv_append_rope_paged(qkv, cos, sin, pos, k_cache, v_cache, block_table)
+                with annotate("extend_attention_paged"):
+                    o, _ = ops.extend_attention_paged(q, k_cache, v_cache, block_table, kv_len, max_kv_len=mk)
+            else:
+                with annotate("kv_append_rope_chunk"):
+                    q = ops.kv_append_rope_chunk(qkv, cos, sin, pos, k_cache, v_cache)
+                with annotate("extend_attention"):
+                    o, _ = ops.extend_attention(q, k_cache, v_cache, kv_len, max_kv_len=mk)
+            o = o.reshape(B, n, H * dk)
+        elif block_table is not None and start > 0:
             if n > 1:
                 raise NotImplementedError("a paged KV cache has no chunk step (n > 1 on a non-empty cache)")
             with annotate("kv_append_rope_paged"):
@@ -665,6 +684,31 @@ class BasicsTransformerLM(nn.Module):
         tokens are reserved first (``cache.reserve(n)``; ``RuntimeError`` when the pool is exhausted),
         the prefill stores its rows through the block table and a step runs ``ops.kv_append_rope_paged``
         and ``ops.decode_attention_paged``. ``chunk=True`` raises ``NotImplementedError`` on it."""
+        start = self._cached_checks(x, cache, chunk)
+        if getattr(cache, "block_table", None) is not None:
+            if chunk:
+                raise NotImplementedError("forward_cached(chunk=True) is not supported on a PagedKVCache")
+            cache.reserve(x.shape[1])
+        return self._forward_cached(x, cache, start)
+
+    @torch.no_grad()
+    def extend_cached(self, x: torch.Tensor, cache) -> torch.Tensor:
+        """:meth:`forward_cached` for ``n >= 1`` tokens on a cache of any length, dense or paged: a prompt
+        prefilled in pieces, the next turn of a conversation, or -- on a ``PagedKVCache`` after
+        ``cache.fork`` -- different (rectangular) suffixes on one shared prefix. An empty cache takes the
+        ordinary prefill and ``n == 1`` the ordinary step; otherwise every layer runs the chunk append
+        and ``ops.extend_attention`` (``ops.extend_attention_paged``), the MFMA kernel of
+        ``csrc/flash_attn/fa_extend.hip``. An FP8 cache raises ``NotImplementedError``."""
+        if getattr(cache, "fp8", False):
+            raise NotImplementedError("extend_cached does not support an FP8 KV cache")
+        start = self._cached_checks(x, cache, True)
+        if getattr(cache, "block_table", None) is not None:
+            cache.reserve(x.shape[1])
+        return self._forward_cached(x, cache, start, extend=True)
+
+    def _cached_checks(self, x: torch.Tensor, cache, multi: bool) -> int:
+        """The argument checks :meth:`forward_cached` and :meth:`extend_cached` share; ``multi``: whether
+        ``n > 1`` tokens may follow a non-empty cache. Returns the cache's length."""
         if getattr(self, "tensor_parallel", None) is not None or any(
                 layer.attn.context_parallel is not None for layer in self.layers):
             raise NotImplementedError("forward_cached does not support tensor / context parallelism")
@@ -678,21 +722,18 @@ class BasicsTransformerLM(nn.Module):
         start = cache.length
         if n < 1:
             raise ValueError("forward_cached needs at least one token")
-        if start > 0 and n > 1 and not chunk:
+        if start > 0 and n > 1 and not multi:
             raise NotImplementedError("chunked prefill (n > 1 on a non-empty cache) is not supported")
         if start + n > min(cache.max_len, self.context_length):
             raise ValueError(f"{start} cached + {n} new tokens exceed the cache (max_len {cache.max_len}, "
                              f"context_length {self.context_length})")
-        if getattr(cache, "block_table", None) is not None:
-            if chunk:
-                raise NotImplementedError("forward_cached(chunk=True) is not supported on a PagedKVCache")
-            cache.reserve(n)
-        return self._forward_cached(x, cache, start)
+        return start
 
-    def _forward_cached(self, x: torch.Tensor, cache, start: int, max_kv_len: int | None = None) -> torch.Tensor:
+    def _forward_cached(self, x: torch.Tensor, cache, start: int, max_kv_len: int | None = None,
+                        extend: bool = False) -> torch.Tensor:
         """The body of :meth:`forward_cached` after its checks: the prefill (``start == 0``) or one
         decode / chunk step (``start > 0``) over the layers, the cache advanced by the tokens of ``x``.
-        ``max_kv_len``: see ``CausalMultiHeadSelfAttention.forward_cached``. Nothing here reads the
+        ``max_kv_len``, ``extend``: see ``CausalMultiHeadSelfAttention.forward_cached``. Nothing here reads the
         host mirror ``cache.length`` or synchronizes the host, so a decode step can be captured into
         a HIP graph (``models/decode_graph.py``)."""
         n = x.shape[1]
@@ -714,7 +755,7 @@ class BasicsTransformerLM(nn.Module):
             for i, layer in enumerate(self.layers):
                 with annotate(f"layer{i}"):
                     a = layer.attn.forward_cached(y, cache.k[i], cache.v[i], start, pos, kv_len, max_kv_len,
-                                                  *scales(i))
+                                                  *scales(i), extend=extend)
                     self._reading(layer.ln2)
                     h, y = ops.add_rmsnorm(h, a, layer.ln2.weight, layer.ln2.eps)
                     f = layer.ffn(y)
@@ -725,7 +766,7 @@ class BasicsTransformerLM(nn.Module):
             for i, layer in enumerate(self.layers):
                 with annotate(f"layer{i}"):
                     h = h + layer.attn.forward_cached(layer.ln1(h), cache.k[i], cache.v[i], start, pos, kv_len,
-                                                      max_kv_len, *scales(i))
+                                                      max_kv_len, *scales(i), extend=extend)
                     h = h + layer.ffn(layer.ln2(h))
             y = self.ln_final(h)
         cache.advance(n)
@@ -752,6 +793,7 @@ class BasicsTransformerLM(nn.Module):
         paged: bool = False,
         page_size: int = 64,
         share_prompt: bool = False,
+        prefill_chunk: int | None = None,
     ) -> torch.Tensor:
         """Autoregressive sampling (``model.py:255-310``) with a working top-k filter (the
         reference's ``masked_fill`` is not in place and its threshold broadcast is wrong for B>1).
@@ -799,8 +841,25 @@ class BasicsTransformerLM(nn.Module):
         ``ValueError``): the prompt is prefilled once, through ``cache.row(0)``, and ``cache.fork(0)`` gives
         the other rows its pages, so B sampled continuations pay one prefill and store the prompt once.
         ``kv_fp8=True`` and ``draft=`` raise with ``paged=True``; with ``graph=<DecodeGraph>`` the graph's own
-        cache is used, whatever its kind."""
+        cache is used, whatever its kind.
+
+        ``prefill_chunk=N`` (with ``use_cache=True``): the prompt is prefilled in pieces of ``N`` tokens, the
+        first by the ordinary prefill and the rest by :meth:`extend_cached`, so the prefill's activations
+        are those of ``N`` tokens whatever the prompt's length. It combines with ``paged=``,
+        ``share_prompt=``, ``graph=`` and ``weights=`` (the graph steps are unchanged) and raises with
+        ``kv_fp8=True`` and with ``draft=``. ``None`` is the one-shot prefill."""
         from .decode_graph import DecodeGraph
+
+        if prefill_chunk is not None:
+            if int(prefill_chunk) != prefill_chunk or prefill_chunk < 1:
+                raise ValueError("generate(prefill_chunk=...) needs an integer >= 1")
+            if not use_cache:
+                raise ValueError("generate(prefill_chunk=...) needs use_cache=True")
+            if kv_fp8:
+                raise NotImplementedError("generate(prefill_chunk=...) does not take kv_fp8=True: the extend step "
+                                          "has no FP8 cache format")
+            if draft is not None:
+                raise ValueError("generate(prefill_chunk=...) does not take draft=")
 
         if (paged or share_prompt) and not use_cache:
             raise ValueError("generate(paged=True / share_prompt=True) needs use_cache=True")
@@ -821,7 +880,7 @@ class BasicsTransformerLM(nn.Module):
             if not use_cache:
                 raise ValueError("generate(sample_on_device=True) needs use_cache=True")
             return self._generate_on_device(x, max_new_tokens, temperature, top_k, eos_token_id, graph, weights, kv_fp8,
-                                            generator, sync_every, paged, page_size, share_prompt)
+                                            generator, sync_every, paged, page_size, share_prompt, prefill_chunk)
         if draft is not None:
             from .speculative import speculative_generate
 
@@ -866,7 +925,7 @@ class BasicsTransformerLM(nn.Module):
         for _ in range(max_new_tokens):
             ctx = x[:, -self.context_length :] if x.size(1) > self.context_length else x
             if cache is not None and cache.length == 0:
-                logits = self._prefill(ctx, cache, share_prompt)
+                logits = self._prefill(ctx, cache, share_prompt, prefill_chunk)
             elif cache is not None and cache.length + 1 == x.size(1) <= self.context_length:
                 if graph is True and dg is None:
                     dg = DecodeGraph(self, cache, capture=True, weights=weights)
@@ -896,17 +955,28 @@ class BasicsTransformerLM(nn.Module):
             return PagedKVCache(self, batch, page_size=page_size, max_len=self.context_length, device=w.device, dtype=cdt)
         return KVCache(self, batch, device=w.device, dtype=cdt, fp8=kv_fp8)
 
-    def _prefill(self, ctx, cache, share_prompt: bool) -> torch.Tensor:
-        """The prompt's last-position logits (B, 1, vocab) (all positions without ``share_prompt``). With
-        ``share_prompt`` (a paged cache, equal rows) row 0 alone is prefilled and forked to the others."""
+    def _prefill(self, ctx, cache, share_prompt: bool, prefill_chunk: int | None = None) -> torch.Tensor:
+        """The prompt's logits (B, n, vocab), whose last position the callers read (n = 1 with
+        ``share_prompt``, the last piece's length with ``prefill_chunk``). With ``share_prompt`` (a paged
+        cache, equal rows) row 0 alone is prefilled and forked to the others. ``prefill_chunk``: the
+        prompt goes in pieces of that many tokens, the first by the prefill, the rest by
+        :meth:`extend_cached`."""
+        if share_prompt:
+            ctx, target = ctx[:1], cache.row(0)
+        else:
+            target = cache
+        step = ctx.size(1) if prefill_chunk is None else int(prefill_chunk)
+        logits = self.forward_cached(ctx[:, :step], target)
+        for s in range(step, ctx.size(1), step):
+            logits = self.extend_cached(ctx[:, s:s + step], target)
         if not share_prompt:
-            return self.forward_cached(ctx, cache)
-        logits = self.forward_cached(ctx[:1], cache.row(0))
+            return logits
         cache.fork(0)
-        return logits[:, -1:].expand(ctx.size(0), -1, -1).contiguous()
+        return logits[:, -1:].expand(cache.batch, -1, -1).contiguous()
 
     def _generate_on_device(self, x, max_new_tokens, temperature, top_k, eos_token_id, graph, weights, kv_fp8,
-                            generator, sync_every, paged=False, page_size=64, share_prompt=False) -> torch.Tensor:
+                            generator, sync_every, paged=False, page_size=64, share_prompt=False,
+                            prefill_chunk=None) -> torch.Tensor:
         """``generate(sample_on_device=True)``: see there."""
         from .decode_graph import DecodeGraph, Sampler
 
@@ -955,7 +1025,7 @@ class BasicsTransformerLM(nn.Module):
             return t[:, None], done
 
         # token 0: the prefill on the prompt's last context_length tokens
-        logits = self._prefill(x[:, -L:] if P > L else x, cache, share_prompt)
+        logits = self._prefill(x[:, -L:] if P > L else x, cache, share_prompt, prefill_chunk)
         tok, done = pick(logits, 0, None)
         out = tok
         # cached steps while the sequence fits the window (and the cache)

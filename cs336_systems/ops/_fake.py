@@ -225,6 +225,19 @@ if hasattr(torch.ops.cs336, "fa_decode_paged"):  # (absent from libraries built 
         return qkv.new_empty((qkv.shape[0], qkv.shape[1], H, D))
 
 
+if hasattr(torch.ops.cs336, "fa_extend"):  # (absent from libraries built before the extend kernel: A/B baselines)
+
+    @register_fake("cs336::fa_extend")
+    def _fa_extend(q, k_cache, v_cache, kv_len, scale, max_kv_len, splits=0):
+        B, n, H, D = q.shape
+        return q.new_empty((B, n, H, D)), q.new_empty((B, n, H), dtype=torch.float32)
+
+    @register_fake("cs336::fa_extend_paged")
+    def _fa_extend_paged(q, k_pool, v_pool, block_table, kv_len, scale, max_kv_len, splits=0):
+        B, n, H, D = q.shape
+        return q.new_empty((B, n, H, D)), q.new_empty((B, n, H), dtype=torch.float32)
+
+
 if hasattr(torch.ops.cs336, "gemm_skinny"):  # (absent from libraries built before the decode graph: A/B baselines)
 
     @register_fake("cs336::gemm_skinny")

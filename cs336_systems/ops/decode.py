@@ -37,6 +37,12 @@ Paged cache (``csrc/flash_attn/fa_decode_paged.hip``): ``decode_attention_paged`
 take ``(num_pages, H, P, d)`` page pools and an int32 ``block_table`` ``(B, T)`` instead of the dense
 planes: row ``j`` of sequence ``b`` is row ``j % P`` of page ``block_table[b, j // P]``. The references
 gather the rows by the table and apply the dense rules; bf16 / fp16 / fp32 only.
+
+Extend attention (``csrc/flash_attn/fa_extend.hip``): ``extend_attention`` / ``extend_attention_paged`` have
+``decode_attention_chunk``'s arguments and semantics (dense planes, or pools and a block table) and run an
+MFMA kernel with a 128-row query tile, for many new tokens on a cache that already holds some: a prompt
+prefilled in pieces, a follow-up turn, different suffixes on a forked prefix. bf16 / fp16 and the four
+head dims run the kernel; fp32 and other head dims run the chunk reference. FP8 planes raise.
 """
 
 from __future__ import annotations
@@ -424,3 +430,47 @@ def kv_append_rope_paged(qkv, cos, sin, pos, k_pool, v_pool, block_table):
                                          k_pool, v_pool, block_table)
         return out[:, 0] if qkv.dim() == 2 else out
     return kv_append_rope_paged_ref(qkv, cos, sin, pos, k_pool, v_pool, block_table)
+
+
+# ---- extend attention (csrc/flash_attn/fa_extend.hip) ----
+def _no_fp8(*planes) -> None:
+    if any(t.dtype == _E4M3 for t in planes):
+        raise ValueError("extend attention has no FP8 cache format: pass bf16 / fp16 / fp32 planes")
+
+
+def extend_attention(q, k_cache, v_cache, kv_len, scale=None, max_kv_len=None, splits=0):
+    """``q`` (B, n, H, d), any ``n >= 1`` -> ``o`` (B, n, H, d), ``lse`` (B, n, H): the semantics of
+    :func:`decode_attention_chunk` on the MFMA kernel. Cache rows at and beyond ``kv_len[b]`` are never
+    loaded. ``max_kv_len`` and ``splits`` as in :func:`decode_attention`; for a given ``splits`` the result
+    is bitwise reproducible and equal to :func:`extend_attention_paged`'s on the same rows."""
+    _no_fp8(k_cache, v_cache)
+    d = q.shape[-1]
+    scale = 1.0 / math.sqrt(d) if scale is None else float(scale)
+    if (use_hip(q, k_cache, v_cache) and d in _DECODE_D and q.dtype in (torch.bfloat16, torch.float16)
+            and q.dim() == 4 and q.shape[1] >= 1 and _cache_layout_ok(k_cache) and _cache_layout_ok(v_cache)):
+        max_len = k_cache.shape[2]
+        bound = max_len if max_kv_len is None else min(int(max_kv_len), max_len)
+        if kv_len.dtype != torch.int32:
+            kv_len = kv_len.to(torch.int32)
+        return ops().fa_extend(q, k_cache, v_cache, kv_len.contiguous(), scale, bound, int(splits))
+    return decode_attention_chunk_ref(q, k_cache, v_cache, kv_len, scale)
+
+
+def extend_attention_paged(q, k_pool, v_pool, block_table, kv_len, scale=None, max_kv_len=None, splits=0):
+    """:func:`extend_attention` on a paged cache (pools and table as in :func:`decode_attention_paged`).
+    The table is read up to entry ``(kv_len[b] - 1) // P`` only, and any placement of the pages gives the
+    same bits."""
+    _no_fp8(k_pool, v_pool)
+    d = q.shape[-1]
+    scale = 1.0 / math.sqrt(d) if scale is None else float(scale)
+    if (use_hip(q, k_pool, v_pool) and d in _DECODE_D and q.dtype in (torch.bfloat16, torch.float16)
+            and q.dim() == 4 and q.shape[1] >= 1 and _paged_layout_ok(k_pool, v_pool, block_table)):
+        max_len = block_table.shape[1] * k_pool.shape[2]
+        bound = max_len if max_kv_len is None else min(int(max_kv_len), max_len)
+        if kv_len.dtype != torch.int32:
+            kv_len = kv_len.to(torch.int32)
+        if block_table.dtype != torch.int32:
+            block_table = block_table.to(torch.int32)
+        return ops().fa_extend_paged(q, k_pool, v_pool, block_table, kv_len.contiguous(), scale, bound, int(splits))
+    return decode_attention_chunk_ref(q, paged_gather(k_pool, block_table), paged_gather(v_pool, block_table), kv_len,
+                                      scale)

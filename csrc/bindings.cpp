@@ -1725,6 +1725,115 @@ at::Tensor kv_append_rope_paged(const at::Tensor& qkv, const at::Tensor& cos, co
   return q_out;
 }
 
+// ------------------------------------------------------------------------------------------
+// Extend attention: n new queries on a dense or paged cache, MFMA (csrc/flash_attn/fa_extend.hip)
+// ------------------------------------------------------------------------------------------
+// the checks both layouts share (q, kv_len, the bound, the grids); returns the contiguous q
+at::Tensor check_extend(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& kv_len,
+                        int64_t max_len, int64_t max_kv_len, int64_t splits, const char* op) {
+  check_cuda(q, "q");
+  TORCH_CHECK(q.dim() == 4, "cs336: ", op, " q must be (B, n, H, D)");
+  const int64_t B = q.size(0), n = q.size(1), H = q.size(2), D = q.size(3);
+  TORCH_CHECK(D == 32 || D == 64 || D == 80 || D == 128, "cs336: ", op, " head dim must be 32, 64, 80 or 128 (got ", D,
+              ")");
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 || q.scalar_type() == at::kHalf, "cs336: ", op, " takes bf16 or fp16");
+  TORCH_CHECK(n >= 1, "cs336: ", op, " needs at least one query row");
+  TORCH_CHECK(q.scalar_type() == k.scalar_type() && q.scalar_type() == v.scalar_type(), "cs336: ", op,
+              " q / k / v dtype mismatch");
+  TORCH_CHECK(k.sizes() == v.sizes() && k.size(1) == H && k.size(3) == D, "cs336: ", op, " k / v must match q's H and D");
+  TORCH_CHECK(k.device() == q.device() && v.device() == q.device() && kv_len.device() == q.device(), "cs336: ", op,
+              " tensors must be on one device");
+  TORCH_CHECK(kv_len.scalar_type() == at::kInt && kv_len.dim() == 1 && kv_len.size(0) == B && kv_len.is_contiguous(),
+              "cs336: kv_len must be a contiguous int32 (B,) device tensor");
+  TORCH_CHECK(max_len < ((int64_t)1 << 30), "cs336: ", op, " max_len must be below 2^30");
+  TORCH_CHECK(max_kv_len >= 0 && max_kv_len <= max_len, "cs336: max_kv_len must be in [0, max_len]");
+  TORCH_CHECK(splits >= 0 && splits <= 64, "cs336: splits must be in [0, 64] (0 = choose)");
+  // both grids in 32 bits: (query tile, b, h, split) workgroups and one merge workgroup per output row
+  TORCH_CHECK(n < ((int64_t)1 << 30) && B * H * ((n + 127) / 128) < ((int64_t)1 << 31) / 64 && B * n * H < ((int64_t)1 << 31),
+              "cs336: ", op, " grid too large");
+  at::Tensor qc = q.contiguous();
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(qc.data_ptr()) % 16) == 0, "cs336: q must be 16-byte aligned");
+  return qc;
+}
+
+// fills what ExtendParams and ExtendPagedParams share; `ws` keeps the partials alive for the caller
+template <typename P>
+void fill_extend(P& p, const at::Tensor& qc, const at::Tensor& k, const at::Tensor& v, at::Tensor& o, at::Tensor& lse,
+                 const at::Tensor& kv_len, int64_t max_len, double scale, int64_t max_kv_len, int64_t splits,
+                 at::Tensor& ws) {
+  const int64_t B = qc.size(0), n = qc.size(1), H = qc.size(2), D = qc.size(3);
+  p.q = qc.data_ptr();
+  p.k = k.data_ptr();
+  p.v = v.data_ptr();
+  p.o = o.data_ptr();
+  p.lse = lse.data_ptr<float>();
+  p.kv_len = kv_len.data_ptr<int>();
+  p.k_sh = k.stride(1); p.k_sn = k.stride(2);
+  p.v_sh = v.stride(1); p.v_sn = v.stride(2);
+  p.B = (int)B; p.n = (int)n; p.H = (int)H; p.D = (int)D; p.max_len = (int)max_len;
+  p.scale = (float)scale;
+  p.splits = splits > 0 ? (int)splits : cs336::fa_extend_splits((int)B, (int)H, (int)n, (int)max_kv_len);
+  if (p.splits > 1) {
+    ws = at::empty({(int64_t)p.splits * B * n * H * (D + 1)}, qc.options().dtype(at::kFloat));
+    p.opart = ws.data_ptr<float>();
+    p.lpart = p.opart + (int64_t)p.splits * B * n * H * D;
+  }
+}
+
+std::tuple<at::Tensor, at::Tensor> fa_extend(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                                             const at::Tensor& kv_len, double scale, int64_t max_kv_len,
+                                             int64_t splits) {
+  check_cache(k_cache, "k_cache");
+  check_cache(v_cache, "v_cache");
+  const int64_t max_len = k_cache.size(2);
+  const at::Tensor qc = check_extend(q, k_cache, v_cache, kv_len, max_len, max_kv_len, splits, "fa_extend");
+  const int64_t B = q.size(0), n = q.size(1), H = q.size(2), D = q.size(3);
+  TORCH_CHECK(k_cache.size(0) == B, "cs336: caches must be (B, H, max_len, D) matching q");
+  c10::DeviceGuard g(q.device());
+  at::Tensor o = at::empty({B, n, H, D}, q.options());
+  at::Tensor lse = at::empty({B, n, H}, q.options().dtype(at::kFloat));
+  if (B * H == 0) return {o, lse};
+  cs336::ExtendParams p;
+  at::Tensor ws;
+  fill_extend(p, qc, k_cache, v_cache, o, lse, kv_len, max_len, scale, max_kv_len, splits, ws);
+  p.k_sb = k_cache.stride(0);
+  p.v_sb = v_cache.stride(0);
+  cs336::fa_extend(p, to_dtype(q), stream());
+  return {o, lse};
+}
+
+std::tuple<at::Tensor, at::Tensor> fa_extend_paged(const at::Tensor& q, const at::Tensor& k_pool,
+                                                   const at::Tensor& v_pool, const at::Tensor& table,
+                                                   const at::Tensor& kv_len, double scale, int64_t max_kv_len,
+                                                   int64_t splits) {
+  TORCH_CHECK(q.dim() == 4, "cs336: fa_extend_paged q must be (B, n, H, D)");
+  const int lg = check_paged(k_pool, v_pool, table, q.size(0), "fa_extend_paged");
+  const int64_t max_len = table.size(1) << lg;
+  const at::Tensor qc = check_extend(q, k_pool, v_pool, kv_len, max_len, max_kv_len, splits, "fa_extend_paged");
+  TORCH_CHECK(table.device() == q.device(), "cs336: fa_extend_paged tensors must be on one device");
+  const int64_t B = q.size(0), n = q.size(1), H = q.size(2), D = q.size(3);
+  c10::DeviceGuard g(q.device());
+  at::Tensor o = at::empty({B, n, H, D}, q.options());
+  at::Tensor lse = at::empty({B, n, H}, q.options().dtype(at::kFloat));
+  if (B * H == 0) return {o, lse};
+  cs336::ExtendPagedParams p;
+  at::Tensor ws;
+  fill_extend(p, qc, k_pool, v_pool, o, lse, kv_len, max_len, scale, max_kv_len, splits, ws);
+  p.table = table.data_ptr<int>();
+  p.table_sb = table.stride(0);
+  p.k_sp = k_pool.stride(0);
+  p.v_sp = v_pool.stride(0);
+  p.num_pages = (int)k_pool.size(0);
+  p.lg_page = lg;
+  cs336::fa_extend_paged(p, to_dtype(q), stream());
+  return {o, lse};
+}
+
+// the split count fa_extend(..., splits=0) picks (benchmarks and profiles report it)
+int64_t fa_extend_splits(int64_t B, int64_t H, int64_t n, int64_t max_kv_len) {
+  return cs336::fa_extend_splits((int)B, (int)H, (int)std::min<int64_t>(n, 1 << 30), (int)max_kv_len);
+}
+
 // the query tile fa_decode_chunk picks for n (benchmarks and profiles report it)
 int64_t fa_decode_chunk_qt(int64_t n) { return cs336::fa_decode_chunk_qt((int)std::min<int64_t>(n, 1 << 20)); }
 
@@ -2185,6 +2294,13 @@ TORCH_LIBRARY(cs336, m) {
       "kv_append_rope_paged(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor(a!) k_pool, Tensor(b!) v_pool, "
       "Tensor block_table) -> Tensor");
   m.def(
+      "fa_extend(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_len, float scale, int max_kv_len, int splits=0) "
+      "-> (Tensor, Tensor)");
+  m.def(
+      "fa_extend_paged(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor kv_len, float scale, "
+      "int max_kv_len, int splits=0) -> (Tensor, Tensor)");
+  m.def("fa_extend_splits(int B, int H, int n, int max_kv_len) -> int", &fa_extend_splits);
+  m.def(
       "fa_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale, Tensor? rope_cos=None, Tensor? rope_sin=None, "
       "Tensor? rope_pos=None) -> (Tensor, Tensor)");
   m.def(
@@ -2260,6 +2376,8 @@ TORCH_LIBRARY_IMPL(cs336, CUDA, m) {
   m.impl("kv_append_rope_chunk_kv8", &kv_append_rope_chunk_kv8);
   m.impl("fa_decode_paged", &fa_decode_paged);
   m.impl("kv_append_rope_paged", &kv_append_rope_paged);
+  m.impl("fa_extend", &fa_extend);
+  m.impl("fa_extend_paged", &fa_extend_paged);
   m.impl("kv_quantize_rows", &kv_quantize_rows);
   m.impl("fa_fwd", &fa_fwd);
   m.impl("fa_fwd_ot", &fa_fwd_ot);

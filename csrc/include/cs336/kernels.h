@@ -356,6 +356,50 @@ struct AppendPagedParams {
 };
 void kv_append_rope_paged(const AppendPagedParams& p, DType t, hipStream_t s);
 
+// ---- extend attention: many new queries on a cache, MFMA (csrc/flash_attn/fa_extend.hip) ----
+// fa_decode_chunk's semantics (query i of n sees keys [0, kv_len[b] - (n - 1 - i)), clamped to
+// [0, max_len]) for any n >= 1 at MFMA rate; bf16 / fp16, D in {32, 64, 80, 128}. Rows at and beyond
+// kv_len[b] are never loaded. Partials and merge are fa_decode_chunk's.
+struct ExtendParams {
+  const void* q;  // (B, n, H, D) contiguous
+  const void* k;  // (B, H, max_len, D) views, as DecodeParams
+  const void* v;
+  void* o;            // (B, n, H, D) contiguous, q's dtype
+  float* lse;         // (B, n, H) natural-log LSE
+  const int* kv_len;  // (B,) device
+  int64_t k_sb, k_sh, k_sn;
+  int64_t v_sb, v_sh, v_sn;
+  int B, n, H, D, max_len;
+  float scale;
+  // splits > 1: fp32 partials opart (splits, B*n*H, D) / lpart (splits, B*n*H), merged by fa_decode_chunk_merge
+  int splits = 1;
+  float* opart = nullptr;
+  float* lpart = nullptr;
+};
+// the same on a page pool: k / v (num_pages, H, P, D) views read through the table, as DecodePagedParams
+struct ExtendPagedParams {
+  const void* q;
+  const void* k;
+  const void* v;
+  void* o;
+  float* lse;
+  const int* kv_len;
+  const int* table;  // (B, max_len / P) device, row stride table_sb; read up to entry (kv_len[b] - 1) >> lg_page
+  int64_t table_sb;
+  int64_t k_sp, k_sh, k_sn;
+  int64_t v_sp, v_sh, v_sn;
+  int B, n, H, D, max_len, num_pages, lg_page;
+  float scale;
+  int splits = 1;
+  float* opart = nullptr;
+  float* lpart = nullptr;
+};
+int fa_extend_query_tiles(int n);  // 128-row query tiles of an n-query step
+// split count the host picks from B * H * query tiles and the upper bound max_kv_len alone
+int fa_extend_splits(int B, int H, int n, int max_kv_len);
+void fa_extend(const ExtendParams& p, DType t, hipStream_t s);
+void fa_extend_paged(const ExtendPagedParams& p, DType t, hipStream_t s);
+
 // ---- FP8 KV cache (csrc/flash_attn/fa_decode_kv8.hip, fa_decode_chunk_kv8.hip) ----
 // A cached row is D OCP e4m3 bytes and one fp32 scale, row = bytes * scale: k / v of the structs are
 // (B, H, max_len, D) byte planes (strides in bytes, rows 16-B aligned, row stride below 2^22) and k_scale / v_scale
