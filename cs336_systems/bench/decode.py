@@ -83,6 +83,14 @@ with ``prefill_chunk`` 256 and 512: wall-clock ms and the peak of ``torch.cuda.m
 weights and the cache.
 
     python -m cs336_systems.bench.decode --extend --json profiles/decode_extend.json
+
+Verify attention (``--verify``; ``csrc/flash_attn/fa_verify.hip``): n in 2 / 4 / 8 / 16 new queries on 512 / 4096 /
+16384 keys, B 1 and 8: ``ops.verify_attention`` and its paged sibling (page 64, seeded random placement) with
+``decode_attention_chunk``, ``extend_attention`` and the one-token ``decode_attention`` alternating in the same run;
+then the replayed xl step of ``DecodeGraph(tokens=t, verify=True)`` against the chunk graph at t 4 / 8 / 16 with 256
+and 4096 tokens cached, B 1 and 8.
+
+    python -m cs336_systems.bench.decode --verify --json profiles/decode_verify.json
 """
 
 from __future__ import annotations
@@ -306,6 +314,99 @@ def extend_row(B: int, H: int, d: int, kv_len: int, n: int, warmup: int = 5, rep
     del q, k, v, pool
     torch.cuda.empty_cache()
     return row
+
+
+VERIFY_N = (2, 4, 8, 16)
+VERIFY_TOKENS = (4, 8, 16)
+
+
+def _verdict(row: dict, name: str, base: str) -> str:
+    """faster / slower only when the q20-q80 ranges of both sides do not overlap."""
+    return ("faster" if row[f"{name}_us_q80"] < row[f"{base}_us_q20"] else
+            "slower" if row[f"{name}_us_q20"] > row[f"{base}_us_q80"] else "same")
+
+
+def verify_attn_row(B: int, H: int, d: int, kv_len: int, n: int, warmup: int = 5, rep: int = 50, page_size: int = 64) -> dict:
+    """``ops.verify_attention`` and its paged sibling beside the chunk kernel, the extend kernel and the one-token
+    decode kernel on the same cache, the five arms alternating: median and q20-q80 in us. Bytes are the K / V rows
+    once plus q and o; ``*_hbm_frac`` is against the achievable read rate."""
+    dev, dt = "cuda", torch.bfloat16
+    torch.manual_seed(0)
+    q = torch.randn(B, n, H, d, device=dev, dtype=dt)
+    k = torch.randn(B, H, kv_len, d, device=dev, dtype=dt)
+    v = torch.randn(B, H, kv_len, d, device=dev, dtype=dt)
+    lens = torch.full((B,), kv_len, dtype=torch.int32, device=dev)
+    pool = _paged_pool(k, v, page_size)
+    q1 = q[:, -1].contiguous()
+    nbytes = 2.0 * B * H * d * (kv_len + n) * k.element_size()
+    row = dict(B=B, H=H, d=d, kv_len=kv_len, n=n, dtype="bf16", page_size=page_size, mbytes=nbytes / 2**20,
+               splits=int(torch.ops.cs336.verify_attention_splits(B, H, n, kv_len)),
+               chunk_query_tile=int(torch.ops.cs336.fa_decode_chunk_qt(n)))
+    arms = {"chunk": lambda: ops.decode_attention_chunk(q, k, v, lens),
+            "verify": lambda: ops.verify_attention(q, k, v, lens),
+            "verify_paged": lambda: ops.verify_attention_paged(q, *pool, lens),
+            "extend": lambda: ops.extend_attention(q, k, v, lens),
+            "decode1": lambda: ops.decode_attention(q1, k, v, lens)}
+    for name, (med, lo, hi) in _alternating(arms, warmup, rep).items():
+        row[f"{name}_us"], row[f"{name}_us_q20"], row[f"{name}_us_q80"] = med, lo, hi
+    for name in ("verify", "verify_paged"):
+        row[f"{name}_gbs"] = nbytes / (row[f"{name}_us"] * 1e-6) / 1e9
+        row[f"{name}_hbm_frac"] = row[f"{name}_gbs"] / HBM_ACHIEVABLE_GBS
+        for base in ("chunk", "extend", "decode1"):
+            row[f"{name}_vs_{base}"] = row[f"{name}_us"] / row[f"{base}_us"]  # below 1: the verify kernel is faster
+            row[f"{name}_verdict_vs_{base}"] = _verdict(row, name, base)
+    oc, _ = ops.decode_attention_chunk(q, k, v, lens)
+    ov, lv = ops.verify_attention(q, k, v, lens)
+    op, lp = ops.verify_attention_paged(q, *pool, lens)
+    row["max_abs_diff_vs_chunk"] = (ov.float() - oc.float()).abs().max().item()
+    row["paged_bitwise"] = bool(torch.equal(op, ov) and torch.equal(lp, lv))
+    del q, k, v, pool
+    torch.cuda.empty_cache()
+    return row
+
+
+def verify_step_rows(model_size: str, batches=(1, 8), cached=(4096, 256), rep: int = 30) -> list[dict]:
+    """Replayed step of ``DecodeGraph(tokens=t)`` on the chunk kernel and with ``verify=True`` on one dense cache,
+    the six graphs interleaved (the cache truncated back after every step), HIP events around the replay."""
+    from ..models import DecodeGraph, build_model
+    from ..models.kv_cache import KVCache
+
+    torch.manual_seed(0)
+    ctx = max(cached) + max(VERIFY_TOKENS)
+    model = build_model(model_size, ctx, device="cuda").to(torch.bfloat16).eval()
+    rows = []
+    for B in batches:
+        x = torch.randint(0, model.vocab_size, (B, ctx), device="cuda")
+        cache = KVCache(model, B)
+        for i in range(0, max(cached), 1024):  # prefill in pieces: bounded activations
+            (model.extend_cached if i else model.forward_cached)(x[:, i:i + 1024], cache)
+        graphs = {(t, ver): DecodeGraph(model, cache, capture=True, tokens=t, verify=ver)
+                  for t in VERIFY_TOKENS for ver in (False, True)}
+        for prefix in sorted(cached, reverse=True):
+            cache.truncate(prefix)
+            times = {key: [] for key in graphs}
+            for r in range(rep + 5):
+                for key, dg in graphs.items():
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    dg.step(x[:, prefix:prefix + key[0]])
+                    b.record()
+                    b.synchronize()
+                    cache.truncate(prefix)
+                    if r >= 5:  # the first rounds warm clocks and caches
+                        times[key].append(a.elapsed_time(b) * 1e3)
+            for t in VERIFY_TOKENS:
+                row = dict(model=model_size, B=B, cached=prefix, tokens=t, dtype="bf16")
+                for ver, name in ((False, "chunk"), (True, "verify")):
+                    ts = sorted(times[(t, ver)])
+                    row[f"{name}_us"], row[f"{name}_us_q20"], row[f"{name}_us_q80"] = (
+                        ts[len(ts) // 2], ts[len(ts) // 5], ts[len(ts) * 4 // 5])
+                row["verify_vs_chunk"] = row["verify_us"] / row["chunk_us"]
+                row["verdict"] = _verdict(row, "verify", "chunk")
+                rows.append(row)
+        del graphs, cache
+        torch.cuda.empty_cache()
+    return rows
 
 
 def extend_prefill_rows(model_size: str, prompt: int = 2048, chunks=(None, 256, 512), runs: int = 5) -> list[dict]:
@@ -652,16 +753,39 @@ def main(argv=None):
                     help="the extend-attention table (extend_attention and its paged sibling against "
                          "decode_attention_chunk; batch default 1 8) and the xl prefill of 2048 tokens in one shot and "
                          "in pieces; no generate arms")
+    ap.add_argument("--verify", action="store_true",
+                    help="the verify-attention table (verify_attention and its paged sibling against the chunk, "
+                         "extend and one-token kernels; batch default 1 8) and the replayed xl verify step against "
+                         "the chunk graph; no generate arms")
     ap.add_argument("--arms", nargs="+", default=["cached", "uncached", "graph"], choices=sorted(ARMS) + ["verify"])
     ap.add_argument("--json", default=None)
     a = ap.parse_args(argv)
-    if a.extend and a.batch == [1, 8, 64]:
+    if (a.extend or a.verify) and a.batch == [1, 8, 64]:
         a.batch = [1, 8]
     if not torch.cuda.is_available():
         raise SystemExit("bench.decode needs a GPU")
     if not ops.load_ext():
         raise SystemExit(ops.load_error())
     out = dict(hbm_achievable_gbs=HBM_ACHIEVABLE_GBS, kernel=[], skinny=[], e2e=[])
+    if a.verify:
+        out.update(verify_attention=[], verify_step=[])
+        if not a.no_kernel:
+            for shape in a.shapes:
+                H, d = (int(s) for s in shape.split("x"))
+                for B in a.batch:
+                    for kv in a.kv_len:
+                        for n in VERIFY_N:
+                            r = verify_attn_row(B, H, d, kv, n, rep=a.rep)
+                            out["verify_attention"].append(r)
+                            print(json.dumps(r), flush=True)
+        if not a.no_e2e:
+            for r in verify_step_rows(a.model, batches=a.batch):
+                out["verify_step"].append(r)
+                print(json.dumps(r), flush=True)
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return out
     if a.extend:
         out.update(extend=[], extend_prefill=[])
         if not a.no_kernel:

@@ -46,6 +46,12 @@ A ``PagedKVCache`` needs no argument either: the captured step reads ``cache.blo
 device-side fills, no read-back -- before replaying. ``weights=`` and ``sampler=`` combine with it;
 ``tokens > 1`` raises (there is no paged chunk kernel).
 
+``verify=True``: the ``tokens=n`` step runs ``ops.verify_attention`` / ``ops.verify_attention_paged``
+(``csrc/flash_attn/fa_verify.hip``, a 16-query MFMA tile that reads the cache once) after the chunk or
+paged append, on a ``KVCache`` or a ``PagedKVCache``: it is how a paged cache takes ``tokens > 1``. ``step``
+reserves the pages before replaying, as the one-token graph does. It raises with ``sampler=`` and on an
+FP8 cache.
+
 ``sampler=Sampler(temperature, top_k, eos_token_id)`` (``tokens == 1`` only) puts the sampling into the
 graph, so that the host neither sees the logits nor issues anything per token but the replay. The
 captured sequence is the model step on ``self.tok``, ``ops.sample_advance`` on its logits
@@ -91,7 +97,7 @@ class DecodeGraph:
     by ``tokens`` (default 1)."""
 
     def __init__(self, model, cache, capture: bool = True, warmup: int = 2, tokens: int = 1, weights=None,
-                 sampler: Sampler | None = None):
+                 sampler: Sampler | None = None, verify: bool = False):
         if getattr(model, "tensor_parallel", None) is not None or any(
                 layer.attn.context_parallel is not None for layer in model.layers):
             raise NotImplementedError("DecodeGraph does not support tensor / context parallelism")
@@ -104,7 +110,12 @@ class DecodeGraph:
         if weights is not None and getattr(weights, "model", None) is not model:
             raise ValueError("weights= was built for a different model")
         self.paged = getattr(cache, "block_table", None) is not None
-        if self.paged and tokens != 1:
+        if verify and sampler is not None:
+            raise ValueError("DecodeGraph(verify=True) is the multi-token verify step: it takes no sampler=")
+        if verify and getattr(cache, "fp8", False):
+            raise NotImplementedError("DecodeGraph(verify=True) does not support an FP8 KV cache")
+        self.verify = bool(verify)
+        if self.paged and tokens != 1 and not verify:
             raise NotImplementedError("DecodeGraph on a PagedKVCache takes tokens == 1: there is no paged chunk step")
         if sampler is not None and tokens != 1:
             raise ValueError("DecodeGraph(sampler=...) samples one token per step: it needs tokens == 1")
@@ -157,7 +168,8 @@ class DecodeGraph:
         ``forward_cached`` (also on an empty cache, where the warm-up's rows land at index 0, unread)
         with the fixed attention bound."""
         with gemm.skinny_decode(weights=self.weights):
-            return self.model._forward_cached(tok, self.cache, max(self.cache.length, 1), self.cache.max_len)
+            return self.model._forward_cached(tok, self.cache, max(self.cache.length, 1), self.cache.max_len,
+                                              verify=self.verify)
 
     @torch.no_grad()
     def _run_sampled(self) -> torch.Tensor:

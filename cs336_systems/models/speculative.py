@@ -28,13 +28,15 @@ from __future__ import annotations
 import torch
 
 from .decode_graph import DecodeGraph
-from .kv_cache import KVCache
+from .kv_cache import KVCache, PagedKVCache
 
 
-def _new_cache(model, batch: int, fp8: bool = False) -> KVCache:
+def _new_cache(model, batch: int, fp8: bool = False, page_size: int | None = None, max_len: int | None = None):
     w = model.lm_head.weight
     dev = w.device.type
     cdt = torch.get_autocast_dtype(dev) if torch.is_autocast_enabled(dev) else w.dtype
+    if page_size is not None:
+        return PagedKVCache(model, batch, page_size=page_size, max_len=max_len, device=w.device, dtype=cdt)
     return KVCache(model, batch, device=w.device, dtype=cdt, fp8=fp8)
 
 
@@ -44,7 +46,8 @@ def _argmax(logits: torch.Tensor) -> torch.Tensor:
 
 @torch.no_grad()
 def speculative_generate(target, draft, x: torch.Tensor, max_new_tokens: int, draft_tokens: int = 4,
-                         eos_token_id: int | None = None, graph: bool = False, kv_fp8: bool = False):
+                         eos_token_id: int | None = None, graph: bool = False, kv_fp8: bool = False,
+                         verify: str = "chunk", paged: bool = False, page_size: int = 64):
     """``(tokens, stats)``: the greedy continuation of ``x`` under ``target`` (B, <= max_new_tokens)
     and ``stats = dict(rounds, proposed, accepted)`` -- speculative rounds, draft tokens proposed and
     proposals accepted.
@@ -52,7 +55,12 @@ def speculative_generate(target, draft, x: torch.Tensor, max_new_tokens: int, dr
     ``graph=True`` (GPU models): the draft's steps replay a ``DecodeGraph(tokens=1)`` and the target's
     verify step a ``DecodeGraph(tokens=draft_tokens + 1)``; rounds with a shrunk ``k`` run eagerly.
     ``kv_fp8=True``: both caches are FP8 ones (``KVCache(fp8=True)``); the output is then the greedy
-    decoding of the target over its FP8 cache."""
+    decoding of the target over its FP8 cache.
+    ``verify="mfma"``: the target's verify step is ``verify_cached`` / ``DecodeGraph(verify=True)``
+    (``ops.verify_attention``, ``csrc/flash_attn/fa_verify.hip``) instead of the chunk step; no FP8 caches.
+    ``paged=True`` (with ``verify="mfma"`` only: the chunk step has no paged form): both caches are
+    ``PagedKVCache`` s of ``page_size``-row pages over the target's window, and every round's
+    ``truncate`` returns the pages of the rejected proposals."""
     if target.lm_head.weight.shape[0] != draft.lm_head.weight.shape[0]:
         raise ValueError("speculative decoding needs one vocabulary: the draft's differs from the target's")
     if draft.context_length < target.context_length:
@@ -62,6 +70,14 @@ def speculative_generate(target, draft, x: torch.Tensor, max_new_tokens: int, dr
         raise ValueError("draft_tokens must be in [1, 15] (a verify step has at most 16 rows per sequence)")
     if not isinstance(graph, bool):
         raise ValueError("speculative decoding takes graph=True or False")
+    if verify not in ("chunk", "mfma"):
+        raise ValueError('speculative decoding takes verify="chunk" or "mfma"')
+    mfma = verify == "mfma"
+    if paged and not mfma:
+        raise NotImplementedError('speculative decoding on paged caches needs verify="mfma": a paged cache has no '
+                                  "chunk step")
+    if kv_fp8 and (mfma or paged):
+        raise NotImplementedError('verify="mfma" and paged=True do not take kv_fp8=True')
     if graph and not (target.lm_head.weight.is_cuda and draft.lm_head.weight.is_cuda):
         raise ValueError("graph=True captures HIP graphs: both models must be on a GPU")
     if x.dim() == 1:
@@ -79,7 +95,8 @@ def speculative_generate(target, draft, x: torch.Tensor, max_new_tokens: int, dr
     # prefill both caches on the prompt (its last ``window`` tokens); the target's last logits give
     # the first token
     ctx = x[:, -window:] if x.size(1) > window else x
-    tc, dc = _new_cache(target, B, kv_fp8), _new_cache(draft, B, kv_fp8)
+    ps = page_size if paged else None
+    tc, dc = _new_cache(target, B, kv_fp8, ps, window), _new_cache(draft, B, kv_fp8, ps, window)
     last = _argmax(target.forward_cached(ctx, tc)[:, -1])[:, None]
     if one and int(last) == eos_token_id:
         return x[:, orig:], stats
@@ -105,8 +122,10 @@ def speculative_generate(target, draft, x: torch.Tensor, max_new_tokens: int, dr
             chunk = torch.cat((last, props), dim=1)
             if graph and k == draft_tokens:
                 if dgt is None:
-                    dgt = DecodeGraph(target, tc, capture=True, tokens=k + 1)
+                    dgt = DecodeGraph(target, tc, capture=True, tokens=k + 1, verify=mfma)
                 t = _argmax(dgt.step(chunk))
+            elif mfma:
+                t = _argmax(target.verify_cached(chunk, tc))
             else:
                 t = _argmax(target.forward_cached(chunk, tc, chunk=True))  # (B, k + 1)
             lead = (props == t[:, :k]).long().cumprod(dim=1).sum(dim=1)  # leading agreements per sequence

@@ -375,7 +375,8 @@ class CausalMultiHeadSelfAttention(nn.Module):
             return self.output_proj(o)
 
     def forward_cached(self, x3, k_cache, v_cache, start: int, pos=None, kv_len=None, max_kv_len=None,
-                       k_scale=None, v_scale=None, block_table=None, *, extend: bool = False) -> torch.Tensor:
+                       k_scale=None, v_scale=None, block_table=None, *, extend: bool = False,
+                       verify: bool = False) -> torch.Tensor:
         """Attention of ``forward_cached`` (inference only). ``x3`` (B, n, d_model); ``k_cache`` /
         ``v_cache`` this layer's (B, H, max_len, dk) cache views. ``start == 0``: prefill -- the
         ordinary causal attention over the n tokens at positions 0..n-1, whose rotated K and V are
@@ -392,7 +393,9 @@ class CausalMultiHeadSelfAttention(nn.Module):
         reserved; the step runs the paged ops and the prefill stores its rows through the table.
         ``extend=True`` (16-bit or fp32 caches): a step of n > 1 tokens runs the chunk append (dense or
         paged) and then ``ops.extend_attention`` / ``ops.extend_attention_paged``, the MFMA kernel, instead
-        of the chunk kernel; it is how a paged cache takes n > 1 tokens at all."""
+        of the chunk kernel; it is how a paged cache takes n > 1 tokens at all. ``verify=True`` is the same
+        step on ``ops.verify_attention`` / ``ops.verify_attention_paged``, whose 16-query tile streams the
+        cache once: the verify step of speculative decoding."""
         B, n, _ = x3.shape
         H, dk = self.num_heads, self.d_k
         w = [self.q_proj.weight, self.k_proj.weight, self.v_proj.weight]
@@ -407,21 +410,24 @@ class CausalMultiHeadSelfAttention(nn.Module):
         sc = dict(k_scale=k_scale, v_scale=v_scale) if fp8 else {}
         if not fp8 and qkv.dtype != k_cache.dtype:
             raise ValueError(f"KV cache dtype {k_cache.dtype} does not match the compute dtype {qkv.dtype}")
-        if extend and start > 0 and n > 1:
+        if (extend or verify) and start > 0 and n > 1:
             if fp8:
-                raise NotImplementedError("the extend step has no FP8 cache format")
+                raise NotImplementedError(f"the {'verify' if verify else 'extend'} step has no FP8 cache format")
+            name = "verify_attention" if verify else "extend_attention"
+            attend, attend_paged = ((ops.verify_attention, ops.verify_attention_paged) if verify else
+                                    (ops.extend_attention, ops.extend_attention_paged))
             mk = start + n if max_kv_len is None else max_kv_len
             cos, sin = self.positional_encoder.cos, self.positional_encoder.sin
             if block_table is not None:
                 with annotate("kv_append_rope_paged"):
                     q = ops.kv_append_rope_paged(qkv, cos, sin, pos, k_cache, v_cache, block_table)
-                with annotate("extend_attention_paged"):
-                    o, _ = ops.extend_attention_paged(q, k_cache, v_cache, block_table, kv_len, max_kv_len=mk)
+                with annotate(name + "_paged"):
+                    o, _ = attend_paged(q, k_cache, v_cache, block_table, kv_len, max_kv_len=mk)
             else:
                 with annotate("kv_append_rope_chunk"):
                     q = ops.kv_append_rope_chunk(qkv, cos, sin, pos, k_cache, v_cache)
-                with annotate("extend_attention"):
-                    o, _ = ops.extend_attention(q, k_cache, v_cache, kv_len, max_kv_len=mk)
+                with annotate(name):
+                    o, _ = attend(q, k_cache, v_cache, kv_len, max_kv_len=mk)
             o = o.reshape(B, n, H * dk)
         elif block_table is not None and start > 0:
             if n > 1:
@@ -706,6 +712,19 @@ class BasicsTransformerLM(nn.Module):
             cache.reserve(x.shape[1])
         return self._forward_cached(x, cache, start, extend=True)
 
+    @torch.no_grad()
+    def verify_cached(self, x: torch.Tensor, cache) -> torch.Tensor:
+        """:meth:`extend_cached` on ``ops.verify_attention`` (``ops.verify_attention_paged``), the kernel of
+        ``csrc/flash_attn/fa_verify.hip`` whose 16-query tile reads the cache once: the verify step of
+        speculative decoding, on a dense or a paged cache. An empty cache takes the ordinary prefill and
+        ``n == 1`` the ordinary step. An FP8 cache raises ``NotImplementedError``."""
+        if getattr(cache, "fp8", False):
+            raise NotImplementedError("verify_cached does not support an FP8 KV cache")
+        start = self._cached_checks(x, cache, True)
+        if getattr(cache, "block_table", None) is not None:
+            cache.reserve(x.shape[1])
+        return self._forward_cached(x, cache, start, verify=True)
+
     def _cached_checks(self, x: torch.Tensor, cache, multi: bool) -> int:
         """The argument checks :meth:`forward_cached` and :meth:`extend_cached` share; ``multi``: whether
         ``n > 1`` tokens may follow a non-empty cache. Returns the cache's length."""
@@ -730,10 +749,10 @@ class BasicsTransformerLM(nn.Module):
         return start
 
     def _forward_cached(self, x: torch.Tensor, cache, start: int, max_kv_len: int | None = None,
-                        extend: bool = False) -> torch.Tensor:
+                        extend: bool = False, verify: bool = False) -> torch.Tensor:
         """The body of :meth:`forward_cached` after its checks: the prefill (``start == 0``) or one
         decode / chunk step (``start > 0``) over the layers, the cache advanced by the tokens of ``x``.
-        ``max_kv_len``, ``extend``: see ``CausalMultiHeadSelfAttention.forward_cached``. Nothing here reads the
+        ``max_kv_len``, ``extend``, ``verify``: see ``CausalMultiHeadSelfAttention.forward_cached``. Nothing here reads the
         host mirror ``cache.length`` or synchronizes the host, so a decode step can be captured into
         a HIP graph (``models/decode_graph.py``)."""
         n = x.shape[1]
@@ -755,7 +774,7 @@ class BasicsTransformerLM(nn.Module):
             for i, layer in enumerate(self.layers):
                 with annotate(f"layer{i}"):
                     a = layer.attn.forward_cached(y, cache.k[i], cache.v[i], start, pos, kv_len, max_kv_len,
-                                                  *scales(i), extend=extend)
+                                                  *scales(i), extend=extend, verify=verify)
                     self._reading(layer.ln2)
                     h, y = ops.add_rmsnorm(h, a, layer.ln2.weight, layer.ln2.eps)
                     f = layer.ffn(y)
@@ -766,7 +785,7 @@ class BasicsTransformerLM(nn.Module):
             for i, layer in enumerate(self.layers):
                 with annotate(f"layer{i}"):
                     h = h + layer.attn.forward_cached(layer.ln1(h), cache.k[i], cache.v[i], start, pos, kv_len,
-                                                      max_kv_len, *scales(i), extend=extend)
+                                                      max_kv_len, *scales(i), extend=extend, verify=verify)
                     h = h + layer.ffn(layer.ln2(h))
             y = self.ln_final(h)
         cache.advance(n)
@@ -794,6 +813,7 @@ class BasicsTransformerLM(nn.Module):
         page_size: int = 64,
         share_prompt: bool = False,
         prefill_chunk: int | None = None,
+        verify: str = "chunk",
     ) -> torch.Tensor:
         """Autoregressive sampling (``model.py:255-310``) with a working top-k filter (the
         reference's ``masked_fill`` is not in place and its threshold broadcast is wrong for B>1).
@@ -847,7 +867,11 @@ class BasicsTransformerLM(nn.Module):
         first by the ordinary prefill and the rest by :meth:`extend_cached`, so the prefill's activations
         are those of ``N`` tokens whatever the prompt's length. It combines with ``paged=``,
         ``share_prompt=``, ``graph=`` and ``weights=`` (the graph steps are unchanged) and raises with
-        ``kv_fp8=True`` and with ``draft=``. ``None`` is the one-shot prefill."""
+        ``kv_fp8=True`` and with ``draft=``. ``None`` is the one-shot prefill.
+
+        ``verify="mfma"`` (with ``draft=``): the target's verify step runs :meth:`verify_cached` (with
+        ``graph=True`` a ``DecodeGraph(verify=True)``) instead of the chunk step. Only then may ``paged=True``
+        be combined with ``draft=``: both caches are paged ones. ``"chunk"`` (default) is the chunk step."""
         from .decode_graph import DecodeGraph
 
         if prefill_chunk is not None:
@@ -865,7 +889,11 @@ class BasicsTransformerLM(nn.Module):
             raise ValueError("generate(paged=True / share_prompt=True) needs use_cache=True")
         if paged and kv_fp8:
             raise ValueError("generate(paged=True) does not take kv_fp8=True: there is no FP8 paged format")
-        if paged and draft is not None:
+        if verify not in ("chunk", "mfma"):
+            raise ValueError('generate(verify=...) takes "chunk" or "mfma"')
+        if verify != "chunk" and draft is None:
+            raise ValueError("generate(verify=...) needs draft=: it names the target's verify step")
+        if paged and draft is not None and verify != "mfma":
             raise NotImplementedError("generate(paged=True) does not take draft=: a paged cache has no chunk step")
         if share_prompt and not paged and not isinstance(graph, DecodeGraph):
             raise ValueError("generate(share_prompt=True) needs paged=True (or a DecodeGraph on a paged cache)")
@@ -893,7 +921,7 @@ class BasicsTransformerLM(nn.Module):
             if weights is not None:
                 raise ValueError("generate(draft=...) does not take weights=")
             return speculative_generate(self, draft, x, max_new_tokens, draft_tokens, eos_token_id, graph,
-                                        kv_fp8=kv_fp8)[0]
+                                        kv_fp8=kv_fp8, verify=verify, paged=paged, page_size=page_size)[0]
 
         if x.dim() == 1:
             x = x.unsqueeze(0)

@@ -238,6 +238,19 @@ if hasattr(torch.ops.cs336, "fa_extend"):  # (absent from libraries built before
         return q.new_empty((B, n, H, D)), q.new_empty((B, n, H), dtype=torch.float32)
 
 
+if hasattr(torch.ops.cs336, "verify_attention"):  # (absent from libraries built before the verify kernel: A/B baselines)
+
+    @register_fake("cs336::verify_attention")
+    def _verify_attention(q, k_cache, v_cache, kv_len, scale, max_kv_len, splits=0):
+        B, n, H, D = q.shape
+        return q.new_empty((B, n, H, D)), q.new_empty((B, n, H), dtype=torch.float32)
+
+    @register_fake("cs336::verify_attention_paged")
+    def _verify_attention_paged(q, k_pool, v_pool, block_table, kv_len, scale, max_kv_len, splits=0):
+        B, n, H, D = q.shape
+        return q.new_empty((B, n, H, D)), q.new_empty((B, n, H), dtype=torch.float32)
+
+
 if hasattr(torch.ops.cs336, "gemm_skinny"):  # (absent from libraries built before the decode graph: A/B baselines)
 
     @register_fake("cs336::gemm_skinny")

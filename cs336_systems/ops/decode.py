@@ -43,6 +43,10 @@ Extend attention (``csrc/flash_attn/fa_extend.hip``): ``extend_attention`` / ``e
 MFMA kernel with a 128-row query tile, for many new tokens on a cache that already holds some: a prompt
 prefilled in pieces, a follow-up turn, different suffixes on a forked prefix. bf16 / fp16 and the four
 head dims run the kernel; fp32 and other head dims run the chunk reference. FP8 planes raise.
+
+Verify attention (``csrc/flash_attn/fa_verify.hip``): ``verify_attention`` / ``verify_attention_paged`` are
+the same calls on a kernel whose query tile is 16 rows (one MFMA 16x16x32 column block) and which streams
+K / V once for the whole tile: the verify step of speculative decoding (``n <= 16``), dense or paged.
 """
 
 from __future__ import annotations
@@ -472,5 +476,45 @@ def extend_attention_paged(q, k_pool, v_pool, block_table, kv_len, scale=None, m
         if block_table.dtype != torch.int32:
             block_table = block_table.to(torch.int32)
         return ops().fa_extend_paged(q, k_pool, v_pool, block_table, kv_len.contiguous(), scale, bound, int(splits))
+    return decode_attention_chunk_ref(q, paged_gather(k_pool, block_table), paged_gather(v_pool, block_table), kv_len,
+                                      scale)
+
+
+# ---- verify attention (csrc/flash_attn/fa_verify.hip) ----
+def verify_attention(q, k_cache, v_cache, kv_len, scale=None, max_kv_len=None, splits=0):
+    """:func:`extend_attention`'s arguments, semantics, layout checks and fallbacks on the 16-query-tile
+    kernel: ``n <= 16`` rows per (batch, head) cost one pass over the cache (larger ``n`` runs
+    ``ceil(n / 16)`` tiles, each over its own key range). For a given ``splits`` the result is bitwise
+    reproducible and equal to :func:`verify_attention_paged`'s on the same rows."""
+    _no_fp8(k_cache, v_cache)
+    d = q.shape[-1]
+    scale = 1.0 / math.sqrt(d) if scale is None else float(scale)
+    if (use_hip(q, k_cache, v_cache) and d in _DECODE_D and q.dtype in (torch.bfloat16, torch.float16)
+            and q.dim() == 4 and q.shape[1] >= 1 and _cache_layout_ok(k_cache) and _cache_layout_ok(v_cache)):
+        max_len = k_cache.shape[2]
+        bound = max_len if max_kv_len is None else min(int(max_kv_len), max_len)
+        if kv_len.dtype != torch.int32:
+            kv_len = kv_len.to(torch.int32)
+        return ops().verify_attention(q, k_cache, v_cache, kv_len.contiguous(), scale, bound, int(splits))
+    return decode_attention_chunk_ref(q, k_cache, v_cache, kv_len, scale)
+
+
+def verify_attention_paged(q, k_pool, v_pool, block_table, kv_len, scale=None, max_kv_len=None, splits=0):
+    """:func:`verify_attention` on a paged cache (pools and table as in :func:`decode_attention_paged`).
+    The table is read up to entry ``(kv_len[b] - 1) // P`` only, and any placement of the pages gives the
+    same bits."""
+    _no_fp8(k_pool, v_pool)
+    d = q.shape[-1]
+    scale = 1.0 / math.sqrt(d) if scale is None else float(scale)
+    if (use_hip(q, k_pool, v_pool) and d in _DECODE_D and q.dtype in (torch.bfloat16, torch.float16)
+            and q.dim() == 4 and q.shape[1] >= 1 and _paged_layout_ok(k_pool, v_pool, block_table)):
+        max_len = block_table.shape[1] * k_pool.shape[2]
+        bound = max_len if max_kv_len is None else min(int(max_kv_len), max_len)
+        if kv_len.dtype != torch.int32:
+            kv_len = kv_len.to(torch.int32)
+        if block_table.dtype != torch.int32:
+            block_table = block_table.to(torch.int32)
+        return ops().verify_attention_paged(q, k_pool, v_pool, block_table, kv_len.contiguous(), scale, bound,
+                                            int(splits))
     return decode_attention_chunk_ref(q, paged_gather(k_pool, block_table), paged_gather(v_pool, block_table), kv_len,
                                       scale)

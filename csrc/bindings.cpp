@@ -1834,6 +1834,72 @@ int64_t fa_extend_splits(int64_t B, int64_t H, int64_t n, int64_t max_kv_len) {
   return cs336::fa_extend_splits((int)B, (int)H, (int)std::min<int64_t>(n, 1 << 30), (int)max_kv_len);
 }
 
+// ------------------------------------------------------------------------------------------
+// Verify attention: up to 16 queries per tile, K / V streamed once (csrc/flash_attn/fa_verify.hip)
+// ------------------------------------------------------------------------------------------
+// extend attention's checks and params; the grid is in 16-row query tiles and the split rule the kernel's
+int64_t verify_splits_checked(const at::Tensor& q, int64_t max_kv_len, int64_t splits, const char* op) {
+  const int64_t B = q.size(0), n = q.size(1), H = q.size(2);
+  TORCH_CHECK(B * H * ((n + 15) / 16) < ((int64_t)1 << 31) / 64, "cs336: ", op, " grid too large");
+  return splits > 0 ? splits : cs336::fa_verify_splits((int)B, (int)H, (int)n, (int)max_kv_len);
+}
+
+std::tuple<at::Tensor, at::Tensor> verify_attention(const at::Tensor& q, const at::Tensor& k_cache,
+                                                    const at::Tensor& v_cache, const at::Tensor& kv_len, double scale,
+                                                    int64_t max_kv_len, int64_t splits) {
+  check_cache(k_cache, "k_cache");
+  check_cache(v_cache, "v_cache");
+  const int64_t max_len = k_cache.size(2);
+  const at::Tensor qc = check_extend(q, k_cache, v_cache, kv_len, max_len, max_kv_len, splits, "verify_attention");
+  const int64_t B = q.size(0), n = q.size(1), H = q.size(2), D = q.size(3);
+  TORCH_CHECK(k_cache.size(0) == B, "cs336: caches must be (B, H, max_len, D) matching q");
+  const int64_t sp = verify_splits_checked(q, max_kv_len, splits, "verify_attention");
+  c10::DeviceGuard g(q.device());
+  at::Tensor o = at::empty({B, n, H, D}, q.options());
+  at::Tensor lse = at::empty({B, n, H}, q.options().dtype(at::kFloat));
+  if (B * H == 0) return {o, lse};
+  cs336::VerifyParams p;
+  at::Tensor ws;
+  fill_extend(p, qc, k_cache, v_cache, o, lse, kv_len, max_len, scale, max_kv_len, sp, ws);
+  p.k_sb = k_cache.stride(0);
+  p.v_sb = v_cache.stride(0);
+  cs336::fa_verify(p, to_dtype(q), stream());
+  return {o, lse};
+}
+
+std::tuple<at::Tensor, at::Tensor> verify_attention_paged(const at::Tensor& q, const at::Tensor& k_pool,
+                                                          const at::Tensor& v_pool, const at::Tensor& table,
+                                                          const at::Tensor& kv_len, double scale, int64_t max_kv_len,
+                                                          int64_t splits) {
+  TORCH_CHECK(q.dim() == 4, "cs336: verify_attention_paged q must be (B, n, H, D)");
+  const int lg = check_paged(k_pool, v_pool, table, q.size(0), "verify_attention_paged");
+  const int64_t max_len = table.size(1) << lg;
+  const at::Tensor qc = check_extend(q, k_pool, v_pool, kv_len, max_len, max_kv_len, splits, "verify_attention_paged");
+  TORCH_CHECK(table.device() == q.device(), "cs336: verify_attention_paged tensors must be on one device");
+  const int64_t B = q.size(0), n = q.size(1), H = q.size(2), D = q.size(3);
+  const int64_t sp = verify_splits_checked(q, max_kv_len, splits, "verify_attention_paged");
+  c10::DeviceGuard g(q.device());
+  at::Tensor o = at::empty({B, n, H, D}, q.options());
+  at::Tensor lse = at::empty({B, n, H}, q.options().dtype(at::kFloat));
+  if (B * H == 0) return {o, lse};
+  cs336::VerifyPagedParams p;
+  at::Tensor ws;
+  fill_extend(p, qc, k_pool, v_pool, o, lse, kv_len, max_len, scale, max_kv_len, sp, ws);
+  p.table = table.data_ptr<int>();
+  p.table_sb = table.stride(0);
+  p.k_sp = k_pool.stride(0);
+  p.v_sp = v_pool.stride(0);
+  p.num_pages = (int)k_pool.size(0);
+  p.lg_page = lg;
+  cs336::fa_verify_paged(p, to_dtype(q), stream());
+  return {o, lse};
+}
+
+// the split count verify_attention(..., splits=0) picks (benchmarks and profiles report it)
+int64_t verify_attention_splits(int64_t B, int64_t H, int64_t n, int64_t max_kv_len) {
+  return cs336::fa_verify_splits((int)B, (int)H, (int)std::min<int64_t>(n, 1 << 30), (int)max_kv_len);
+}
+
 // the query tile fa_decode_chunk picks for n (benchmarks and profiles report it)
 int64_t fa_decode_chunk_qt(int64_t n) { return cs336::fa_decode_chunk_qt((int)std::min<int64_t>(n, 1 << 20)); }
 
@@ -2301,6 +2367,13 @@ TORCH_LIBRARY(cs336, m) {
       "int max_kv_len, int splits=0) -> (Tensor, Tensor)");
   m.def("fa_extend_splits(int B, int H, int n, int max_kv_len) -> int", &fa_extend_splits);
   m.def(
+      "verify_attention(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_len, float scale, int max_kv_len, "
+      "int splits=0) -> (Tensor, Tensor)");
+  m.def(
+      "verify_attention_paged(Tensor q, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor kv_len, float scale, "
+      "int max_kv_len, int splits=0) -> (Tensor, Tensor)");
+  m.def("verify_attention_splits(int B, int H, int n, int max_kv_len) -> int", &verify_attention_splits);
+  m.def(
       "fa_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale, Tensor? rope_cos=None, Tensor? rope_sin=None, "
       "Tensor? rope_pos=None) -> (Tensor, Tensor)");
   m.def(
@@ -2378,6 +2451,8 @@ TORCH_LIBRARY_IMPL(cs336, CUDA, m) {
   m.impl("kv_append_rope_paged", &kv_append_rope_paged);
   m.impl("fa_extend", &fa_extend);
   m.impl("fa_extend_paged", &fa_extend_paged);
+  m.impl("verify_attention", &verify_attention);
+  m.impl("verify_attention_paged", &verify_attention_paged);
   m.impl("kv_quantize_rows", &kv_quantize_rows);
   m.impl("fa_fwd", &fa_fwd);
   m.impl("fa_fwd_ot", &fa_fwd_ot);

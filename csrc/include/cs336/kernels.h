@@ -400,6 +400,17 @@ int fa_extend_splits(int B, int H, int n, int max_kv_len);
 void fa_extend(const ExtendParams& p, DType t, hipStream_t s);
 void fa_extend_paged(const ExtendPagedParams& p, DType t, hipStream_t s);
 
+// ---- verify attention: up to 16 new queries per tile, K / V streamed once (csrc/flash_attn/fa_verify.hip) ----
+// The same arguments, semantics, partial layout and merge as extend attention, so the same structs: a
+// 16-query tile on 16x16x32 MFMA for the verify step of speculative decoding (n <= 16; larger n runs
+// ceil(n / 16) tiles, each reading its key range).
+typedef ExtendParams VerifyParams;
+typedef ExtendPagedParams VerifyPagedParams;
+int fa_verify_query_tiles(int n);  // 16-row query tiles of an n-query step
+int fa_verify_splits(int B, int H, int n, int max_kv_len);
+void fa_verify(const VerifyParams& p, DType t, hipStream_t s);
+void fa_verify_paged(const VerifyPagedParams& p, DType t, hipStream_t s);
+
 // ---- FP8 KV cache (csrc/flash_attn/fa_decode_kv8.hip, fa_decode_chunk_kv8.hip) ----
 // A cached row is D OCP e4m3 bytes and one fp32 scale, row = bytes * scale: k / v of the structs are
 // (B, H, max_len, D) byte planes (strides in bytes, rows 16-B aligned, row stride below 2^22) and k_scale / v_scale
