@@ -91,6 +91,12 @@ then the replayed xl step of ``DecodeGraph(tokens=t, verify=True)`` against the 
 and 4096 tokens cached, B 1 and 8.
 
     python -m cs336_systems.bench.decode --verify --json profiles/decode_verify.json
+
+Verify attention on the FP8 cache (``--verify --kv-fp8``; ``csrc/flash_attn/fa_verify_kv8.hip``): the same shapes;
+``ops.verify_attention`` on FP8 planes, ``decode_attention_chunk`` on the same planes and the bf16 verify kernel on
+the unquantized rows, alternating in the same run.
+
+    python -m cs336_systems.bench.decode --verify --kv-fp8 --json profiles/decode_verify_kv8.json
 """
 
 from __future__ import annotations
@@ -361,6 +367,40 @@ def verify_attn_row(B: int, H: int, d: int, kv_len: int, n: int, warmup: int = 5
     row["max_abs_diff_vs_chunk"] = (ov.float() - oc.float()).abs().max().item()
     row["paged_bitwise"] = bool(torch.equal(op, ov) and torch.equal(lp, lv))
     del q, k, v, pool
+    torch.cuda.empty_cache()
+    return row
+
+
+def verify_kv8_row(B: int, H: int, d: int, kv_len: int, n: int, warmup: int = 5, rep: int = 50) -> dict:
+    """``ops.verify_attention`` on an FP8 cache (``fa_verify_kv8.hip``) beside ``decode_attention_chunk`` on the
+    same FP8 cache and the bf16 verify kernel on the rows the cache was quantized from, the three arms
+    alternating: median and q20-q80 in us. Bytes are the four FP8 planes once plus q and o."""
+    dev, dt = "cuda", torch.bfloat16
+    torch.manual_seed(0)
+    q = torch.randn(B, n, H, d, device=dev, dtype=dt)
+    k = torch.randn(B, H, kv_len, d, device=dev, dtype=dt)
+    v = torch.randn(B, H, kv_len, d, device=dev, dtype=dt)
+    lens = torch.full((B,), kv_len, dtype=torch.int32, device=dev)
+    k8, v8, ks, vs, nbytes = _kv8_planes(k, v)
+    nbytes += 2.0 * B * H * d * n * q.element_size()
+    sc = dict(k_scale=ks, v_scale=vs)
+    row = dict(B=B, H=H, d=d, kv_len=kv_len, n=n, dtype="bf16", mbytes=nbytes / 2**20,
+               splits=int(torch.ops.cs336.verify_attention_splits(B, H, n, kv_len)),
+               chunk_kv8_query_tiles=-(-n // 4))
+    arms = {"verify_kv8": lambda: ops.verify_attention(q, k8, v8, lens, **sc),
+            "chunk_kv8": lambda: ops.decode_attention_chunk(q, k8, v8, lens, **sc),
+            "verify_bf16": lambda: ops.verify_attention(q, k, v, lens)}
+    for name, (med, lo, hi) in _alternating(arms, warmup, rep).items():
+        row[f"{name}_us"], row[f"{name}_us_q20"], row[f"{name}_us_q80"] = med, lo, hi
+    row["verify_kv8_gbs"] = nbytes / (row["verify_kv8_us"] * 1e-6) / 1e9
+    row["verify_kv8_hbm_frac"] = row["verify_kv8_gbs"] / HBM_ACHIEVABLE_GBS
+    for base in ("chunk_kv8", "verify_bf16"):
+        row[f"verify_kv8_vs_{base}"] = row["verify_kv8_us"] / row[f"{base}_us"]  # below 1: the new kernel is faster
+        row[f"verdict_vs_{base}"] = _verdict(row, "verify_kv8", base)
+    o8, _ = ops.verify_attention(q, k8, v8, lens, **sc)
+    oc, _ = ops.decode_attention_chunk(q, k8, v8, lens, **sc)
+    row["max_abs_diff_vs_chunk_kv8"] = (o8.float() - oc.float()).abs().max().item()
+    del q, k, v, k8, v8, ks, vs
     torch.cuda.empty_cache()
     return row
 
@@ -767,6 +807,20 @@ def main(argv=None):
     if not ops.load_ext():
         raise SystemExit(ops.load_error())
     out = dict(hbm_achievable_gbs=HBM_ACHIEVABLE_GBS, kernel=[], skinny=[], e2e=[])
+    if a.verify and a.kv_fp8:
+        out.update(verify_kv8=[])
+        for shape in a.shapes:
+            H, d = (int(s) for s in shape.split("x"))
+            for B in a.batch:
+                for kv in a.kv_len:
+                    for n in VERIFY_N:
+                        r = verify_kv8_row(B, H, d, kv, n, rep=a.rep)
+                        out["verify_kv8"].append(r)
+                        print(json.dumps(r), flush=True)
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return out
     if a.verify:
         out.update(verify_attention=[], verify_step=[])
         if not a.no_kernel:

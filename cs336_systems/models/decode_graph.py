@@ -49,8 +49,9 @@ device-side fills, no read-back -- before replaying. ``weights=`` and ``sampler=
 ``verify=True``: the ``tokens=n`` step runs ``ops.verify_attention`` / ``ops.verify_attention_paged``
 (``csrc/flash_attn/fa_verify.hip``, a 16-query MFMA tile that reads the cache once) after the chunk or
 paged append, on a ``KVCache`` or a ``PagedKVCache``: it is how a paged cache takes ``tokens > 1``. ``step``
-reserves the pages before replaying, as the one-token graph does. It raises with ``sampler=`` and on an
-FP8 cache.
+reserves the pages before replaying, as the one-token graph does. It raises with ``sampler=``. On a
+``KVCache(fp8=True)`` the captured step is the FP8 one (``csrc/flash_attn/fa_verify_kv8.hip``): a graph is
+tied to its cache's format, so there is nothing to opt into.
 
 ``sampler=Sampler(temperature, top_k, eos_token_id)`` (``tokens == 1`` only) puts the sampling into the
 graph, so that the host neither sees the logits nor issues anything per token but the replay. The
@@ -112,8 +113,6 @@ class DecodeGraph:
         self.paged = getattr(cache, "block_table", None) is not None
         if verify and sampler is not None:
             raise ValueError("DecodeGraph(verify=True) is the multi-token verify step: it takes no sampler=")
-        if verify and getattr(cache, "fp8", False):
-            raise NotImplementedError("DecodeGraph(verify=True) does not support an FP8 KV cache")
         self.verify = bool(verify)
         if self.paged and tokens != 1 and not verify:
             raise NotImplementedError("DecodeGraph on a PagedKVCache takes tokens == 1: there is no paged chunk step")

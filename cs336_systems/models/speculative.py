@@ -57,7 +57,8 @@ def speculative_generate(target, draft, x: torch.Tensor, max_new_tokens: int, dr
     ``kv_fp8=True``: both caches are FP8 ones (``KVCache(fp8=True)``); the output is then the greedy
     decoding of the target over its FP8 cache.
     ``verify="mfma"``: the target's verify step is ``verify_cached`` / ``DecodeGraph(verify=True)``
-    (``ops.verify_attention``, ``csrc/flash_attn/fa_verify.hip``) instead of the chunk step; no FP8 caches.
+    (``ops.verify_attention``, ``csrc/flash_attn/fa_verify.hip``) instead of the chunk step; with
+    ``kv_fp8=True`` it is the FP8 verify step (``csrc/flash_attn/fa_verify_kv8.hip``).
     ``paged=True`` (with ``verify="mfma"`` only: the chunk step has no paged form): both caches are
     ``PagedKVCache`` s of ``page_size``-row pages over the target's window, and every round's
     ``truncate`` returns the pages of the rejected proposals."""
@@ -76,8 +77,8 @@ def speculative_generate(target, draft, x: torch.Tensor, max_new_tokens: int, dr
     if paged and not mfma:
         raise NotImplementedError('speculative decoding on paged caches needs verify="mfma": a paged cache has no '
                                   "chunk step")
-    if kv_fp8 and (mfma or paged):
-        raise NotImplementedError('verify="mfma" and paged=True do not take kv_fp8=True')
+    if kv_fp8 and paged:
+        raise NotImplementedError("paged=True does not take kv_fp8=True: there is no FP8 paged format")
     if graph and not (target.lm_head.weight.is_cuda and draft.lm_head.weight.is_cuda):
         raise ValueError("graph=True captures HIP graphs: both models must be on a GPU")
     if x.dim() == 1:
@@ -125,7 +126,7 @@ def speculative_generate(target, draft, x: torch.Tensor, max_new_tokens: int, dr
                     dgt = DecodeGraph(target, tc, capture=True, tokens=k + 1, verify=mfma)
                 t = _argmax(dgt.step(chunk))
             elif mfma:
-                t = _argmax(target.verify_cached(chunk, tc))
+                t = _argmax(target.verify_cached(chunk, tc, kv_fp8=kv_fp8))
             else:
                 t = _argmax(target.forward_cached(chunk, tc, chunk=True))  # (B, k + 1)
             lead = (props == t[:, :k]).long().cumprod(dim=1).sum(dim=1)  # leading agreements per sequence

@@ -395,7 +395,8 @@ class CausalMultiHeadSelfAttention(nn.Module):
         paged) and then ``ops.extend_attention`` / ``ops.extend_attention_paged``, the MFMA kernel, instead
         of the chunk kernel; it is how a paged cache takes n > 1 tokens at all. ``verify=True`` is the same
         step on ``ops.verify_attention`` / ``ops.verify_attention_paged``, whose 16-query tile streams the
-        cache once: the verify step of speculative decoding."""
+        cache once: the verify step of speculative decoding. It also takes a dense FP8 cache (the chunk
+        append and ``ops.verify_attention`` with the scale views, ``csrc/flash_attn/fa_verify_kv8.hip``)."""
         B, n, _ = x3.shape
         H, dk = self.num_heads, self.d_k
         w = [self.q_proj.weight, self.k_proj.weight, self.v_proj.weight]
@@ -411,8 +412,8 @@ class CausalMultiHeadSelfAttention(nn.Module):
         if not fp8 and qkv.dtype != k_cache.dtype:
             raise ValueError(f"KV cache dtype {k_cache.dtype} does not match the compute dtype {qkv.dtype}")
         if (extend or verify) and start > 0 and n > 1:
-            if fp8:
-                raise NotImplementedError(f"the {'verify' if verify else 'extend'} step has no FP8 cache format")
+            if fp8 and (not verify or block_table is not None):  # (FP8: the dense verify step only)
+                raise NotImplementedError("the extend step and paged caches have no FP8 cache format")
             name = "verify_attention" if verify else "extend_attention"
             attend, attend_paged = ((ops.verify_attention, ops.verify_attention_paged) if verify else
                                     (ops.extend_attention, ops.extend_attention_paged))
@@ -425,9 +426,9 @@ class CausalMultiHeadSelfAttention(nn.Module):
                     o, _ = attend_paged(q, k_cache, v_cache, block_table, kv_len, max_kv_len=mk)
             else:
                 with annotate("kv_append_rope_chunk"):
-                    q = ops.kv_append_rope_chunk(qkv, cos, sin, pos, k_cache, v_cache)
+                    q = ops.kv_append_rope_chunk(qkv, cos, sin, pos, k_cache, v_cache, **sc)
                 with annotate(name):
-                    o, _ = attend(q, k_cache, v_cache, kv_len, max_kv_len=mk)
+                    o, _ = attend(q, k_cache, v_cache, kv_len, max_kv_len=mk, **sc)
             o = o.reshape(B, n, H * dk)
         elif block_table is not None and start > 0:
             if n > 1:
@@ -713,13 +714,18 @@ class BasicsTransformerLM(nn.Module):
         return self._forward_cached(x, cache, start, extend=True)
 
     @torch.no_grad()
-    def verify_cached(self, x: torch.Tensor, cache) -> torch.Tensor:
+    def verify_cached(self, x: torch.Tensor, cache, *, kv_fp8: bool = False) -> torch.Tensor:
         """:meth:`extend_cached` on ``ops.verify_attention`` (``ops.verify_attention_paged``), the kernel of
         ``csrc/flash_attn/fa_verify.hip`` whose 16-query tile reads the cache once: the verify step of
         speculative decoding, on a dense or a paged cache. An empty cache takes the ordinary prefill and
-        ``n == 1`` the ordinary step. An FP8 cache raises ``NotImplementedError``."""
-        if getattr(cache, "fp8", False):
-            raise NotImplementedError("verify_cached does not support an FP8 KV cache")
+        ``n == 1`` the ordinary step. An FP8 cache raises ``NotImplementedError`` unless ``kv_fp8=True``
+        says it is meant: then ``cache`` must be a ``KVCache(fp8=True)`` (else ``ValueError``) and the step
+        appends quantized rows and attends through ``csrc/flash_attn/fa_verify_kv8.hip``."""
+        fp8 = bool(getattr(cache, "fp8", False))
+        if kv_fp8 and (not fp8 or getattr(cache, "block_table", None) is not None):
+            raise ValueError("verify_cached(kv_fp8=True) takes a KVCache(fp8=True)")
+        if fp8 and not kv_fp8:
+            raise NotImplementedError("verify_cached on an FP8 KV cache needs kv_fp8=True")
         start = self._cached_checks(x, cache, True)
         if getattr(cache, "block_table", None) is not None:
             cache.reserve(x.shape[1])
@@ -871,7 +877,8 @@ class BasicsTransformerLM(nn.Module):
 
         ``verify="mfma"`` (with ``draft=``): the target's verify step runs :meth:`verify_cached` (with
         ``graph=True`` a ``DecodeGraph(verify=True)``) instead of the chunk step. Only then may ``paged=True``
-        be combined with ``draft=``: both caches are paged ones. ``"chunk"`` (default) is the chunk step."""
+        be combined with ``draft=``: both caches are paged ones. With ``kv_fp8=True`` (dense caches) it is the
+        FP8 verify step of ``csrc/flash_attn/fa_verify_kv8.hip``. ``"chunk"`` (default) is the chunk step."""
         from .decode_graph import DecodeGraph
 
         if prefill_chunk is not None:

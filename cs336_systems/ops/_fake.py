@@ -251,6 +251,14 @@ if hasattr(torch.ops.cs336, "verify_attention"):  # (absent from libraries built
         return q.new_empty((B, n, H, D)), q.new_empty((B, n, H), dtype=torch.float32)
 
 
+if hasattr(torch.ops.cs336, "verify_attention_kv8"):  # (absent from libraries built before the FP8 verify kernel)
+
+    @register_fake("cs336::verify_attention_kv8")
+    def _verify_attention_kv8(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale, max_kv_len, splits=0):
+        B, n, H, D = q.shape
+        return q.new_empty((B, n, H, D)), q.new_empty((B, n, H), dtype=torch.float32)
+
+
 if hasattr(torch.ops.cs336, "gemm_skinny"):  # (absent from libraries built before the decode graph: A/B baselines)
 
     @register_fake("cs336::gemm_skinny")

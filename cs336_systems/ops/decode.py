@@ -47,6 +47,8 @@ head dims run the kernel; fp32 and other head dims run the chunk reference. FP8 
 Verify attention (``csrc/flash_attn/fa_verify.hip``): ``verify_attention`` / ``verify_attention_paged`` are
 the same calls on a kernel whose query tile is 16 rows (one MFMA 16x16x32 column block) and which streams
 K / V once for the whole tile: the verify step of speculative decoding (``n <= 16``), dense or paged.
+``verify_attention`` also takes a dense FP8 cache with ``k_scale`` / ``v_scale``
+(``csrc/flash_attn/fa_verify_kv8.hip``); the paged call has no FP8 format and raises.
 """
 
 from __future__ import annotations
@@ -481,14 +483,30 @@ def extend_attention_paged(q, k_pool, v_pool, block_table, kv_len, scale=None, m
 
 
 # ---- verify attention (csrc/flash_attn/fa_verify.hip) ----
-def verify_attention(q, k_cache, v_cache, kv_len, scale=None, max_kv_len=None, splits=0):
+def verify_attention(q, k_cache, v_cache, kv_len, scale=None, max_kv_len=None, splits=0, *, k_scale=None,
+                     v_scale=None):
     """:func:`extend_attention`'s arguments, semantics, layout checks and fallbacks on the 16-query-tile
     kernel: ``n <= 16`` rows per (batch, head) cost one pass over the cache (larger ``n`` runs
     ``ceil(n / 16)`` tiles, each over its own key range). For a given ``splits`` the result is bitwise
-    reproducible and equal to :func:`verify_attention_paged`'s on the same rows."""
-    _no_fp8(k_cache, v_cache)
+    reproducible and equal to :func:`verify_attention_paged`'s on the same rows.
+
+    ``k_scale`` / ``v_scale``: the scale planes of a ``float8_e4m3fn`` cache (dense only), read by the
+    kernel of ``csrc/flash_attn/fa_verify_kv8.hip``: the same tile over the half-size rows. bf16 / fp16
+    ``q`` and the four head dims run it; anything else runs the chunk reference on the dequantized planes."""
     d = q.shape[-1]
     scale = 1.0 / math.sqrt(d) if scale is None else float(scale)
+    if _kv8(k_cache, v_cache, k_scale, v_scale):
+        if (use_hip(q, k_cache, v_cache) and d in _DECODE_D and q.dtype in (torch.bfloat16, torch.float16)
+                and q.dim() == 4 and q.shape[1] >= 1 and _cache_layout_ok(k_cache) and _cache_layout_ok(v_cache)
+                and _scale_layout_ok(k_scale) and _scale_layout_ok(v_scale)):
+            max_len = k_cache.shape[2]
+            bound = max_len if max_kv_len is None else min(int(max_kv_len), max_len)
+            if kv_len.dtype != torch.int32:
+                kv_len = kv_len.to(torch.int32)
+            return ops().verify_attention_kv8(q, k_cache, v_cache, k_scale, v_scale, kv_len.contiguous(), scale, bound,
+                                              int(splits))
+        return decode_attention_chunk_ref(q, kv_dequantize(k_cache, k_scale), kv_dequantize(v_cache, v_scale), kv_len,
+                                          scale)
     if (use_hip(q, k_cache, v_cache) and d in _DECODE_D and q.dtype in (torch.bfloat16, torch.float16)
             and q.dim() == 4 and q.shape[1] >= 1 and _cache_layout_ok(k_cache) and _cache_layout_ok(v_cache)):
         max_len = k_cache.shape[2]

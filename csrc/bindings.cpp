@@ -2038,6 +2038,45 @@ std::tuple<at::Tensor, at::Tensor> fa_decode_chunk_kv8(const at::Tensor& q, cons
   return {o, lse};
 }
 
+// verify attention on the FP8 format (csrc/flash_attn/fa_verify_kv8.hip): fa_decode_chunk_kv8's plane
+// checks, verify_attention's q / grid checks and split rule
+std::tuple<at::Tensor, at::Tensor> verify_attention_kv8(const at::Tensor& q, const at::Tensor& k_cache,
+                                                        const at::Tensor& v_cache, const at::Tensor& k_scale,
+                                                        const at::Tensor& v_scale, const at::Tensor& kv_len,
+                                                        double scale, int64_t max_kv_len, int64_t splits) {
+  const char* op = "verify_attention_kv8";
+  check_cuda(q, "q");
+  cs336::VerifyKv8Params pp;
+  pp.sc = check_kv8(k_cache, v_cache, k_scale, v_scale);
+  TORCH_CHECK(q.dim() == 4, "cs336: ", op, " q must be (B, n, H, D)");
+  const int64_t B = q.size(0), n = q.size(1), H = q.size(2), D = q.size(3), max_len = k_cache.size(2);
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 || q.scalar_type() == at::kHalf, "cs336: ", op, " takes bf16 or fp16 q");
+  TORCH_CHECK(n >= 1, "cs336: ", op, " needs at least one query row");
+  TORCH_CHECK(k_cache.size(0) == B && k_cache.size(1) == H && k_cache.size(3) == D,
+              "cs336: caches must be (B, H, max_len, D) matching q");
+  TORCH_CHECK(k_cache.device() == q.device() && kv_len.device() == q.device(), "cs336: ", op,
+              " tensors must be on one device");
+  TORCH_CHECK(kv_len.scalar_type() == at::kInt && kv_len.dim() == 1 && kv_len.size(0) == B && kv_len.is_contiguous(),
+              "cs336: kv_len must be a contiguous int32 (B,) device tensor");
+  TORCH_CHECK(max_len < ((int64_t)1 << 30), "cs336: ", op, " max_len must be below 2^30");
+  TORCH_CHECK(max_kv_len >= 0 && max_kv_len <= max_len, "cs336: max_kv_len must be in [0, max_len]");
+  TORCH_CHECK(splits >= 0 && splits <= 64, "cs336: splits must be in [0, 64] (0 = choose)");
+  TORCH_CHECK(n < ((int64_t)1 << 30) && B * n * H < ((int64_t)1 << 31), "cs336: ", op, " grid too large");
+  const int64_t sp = verify_splits_checked(q, max_kv_len, splits, op);
+  c10::DeviceGuard g(q.device());
+  at::Tensor qc = q.contiguous();
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(qc.data_ptr()) % 16) == 0, "cs336: q must be 16-byte aligned");
+  at::Tensor o = at::empty({B, n, H, D}, q.options());
+  at::Tensor lse = at::empty({B, n, H}, q.options().dtype(at::kFloat));
+  if (B * H == 0) return {o, lse};
+  at::Tensor ws;
+  fill_extend(pp.base, qc, k_cache, v_cache, o, lse, kv_len, max_len, scale, max_kv_len, sp, ws);
+  pp.base.k_sb = k_cache.stride(0);
+  pp.base.v_sb = v_cache.stride(0);
+  cs336::fa_verify_kv8(pp, to_dtype(q), stream());
+  return {o, lse};
+}
+
 // qkv (B, 3*H*D) -> q_out (B, H, D), or (B, n, 3*H*D) -> (B, n, H, D)
 at::Tensor append_kv8(const at::Tensor& qkv, bool chunk, const at::Tensor& cos, const at::Tensor& sin,
                       const at::Tensor& pos, at::Tensor& k_cache, at::Tensor& v_cache, at::Tensor& k_scale,
@@ -2374,6 +2413,9 @@ TORCH_LIBRARY(cs336, m) {
       "int max_kv_len, int splits=0) -> (Tensor, Tensor)");
   m.def("verify_attention_splits(int B, int H, int n, int max_kv_len) -> int", &verify_attention_splits);
   m.def(
+      "verify_attention_kv8(Tensor q, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, Tensor kv_len, "
+      "float scale, int max_kv_len, int splits=0) -> (Tensor, Tensor)");
+  m.def(
       "fa_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale, Tensor? rope_cos=None, Tensor? rope_sin=None, "
       "Tensor? rope_pos=None) -> (Tensor, Tensor)");
   m.def(
@@ -2453,6 +2495,7 @@ TORCH_LIBRARY_IMPL(cs336, CUDA, m) {
   m.impl("fa_extend_paged", &fa_extend_paged);
   m.impl("verify_attention", &verify_attention);
   m.impl("verify_attention_paged", &verify_attention_paged);
+  m.impl("verify_attention_kv8", &verify_attention_kv8);
   m.impl("kv_quantize_rows", &kv_quantize_rows);
   m.impl("fa_fwd", &fa_fwd);
   m.impl("fa_fwd_ot", &fa_fwd_ot);

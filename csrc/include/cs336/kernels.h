@@ -439,6 +439,13 @@ int fa_decode_kv8_key_tile(int D, int n);
 int fa_decode_kv8_splits(int B, int H, int D, int n, int max_kv_len);
 void fa_decode_kv8(const DecodeKv8Params& p, DType t, hipStream_t s);
 void fa_decode_chunk_kv8(const DecodeChunkKv8Params& p, DType t, hipStream_t s);
+// fa_verify on the FP8 format (csrc/flash_attn/fa_verify_kv8.hip): the 16-query MFMA tile reads the byte
+// rows once; q / o bf16 or fp16, dense planes, the split heuristic is fa_verify_splits
+struct VerifyKv8Params {
+  VerifyParams base;
+  Kv8Scales sc;
+};
+void fa_verify_kv8(const VerifyKv8Params& p, DType t, hipStream_t s);
 // kv_append_rope / kv_append_rope_chunk on the FP8 format: rotated q -> q_out in qkv's type; the fp32
 // rotated k and the plain v row are quantized (one rounding) into row pos[b] + i of the four planes.
 // One kernel serves both (the single append is base.n == 1, base.qkv_sn unused).
