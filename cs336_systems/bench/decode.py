@@ -594,6 +594,114 @@ def skinny_row(model_size: str, name: str, M: int, N: int, K: int, warmup: int =
     return row
 
 
+WQ_M = (32, 64, 128)
+
+
+def wq_row(model_size: str, name: str, M: int, N: int, K: int, warmup: int = 5, rep: int = 50) -> dict:
+    """One projection at 17..128 rows, the arms alternating in one run: the weight-only GEMM of
+    ``csrc/gemm/gemm_wq.hip`` in both formats (``fp8``, ``fp4``); the path the same call took before it
+    (``fp8_old`` / ``fp4_old``: dequantize, hipBLASLt with an fp32 result, scale, cast -- as
+    ``ops.skinny_linear_*`` ran it and still runs above 128 rows); ``torch.mm`` on the bf16 weight (``mm``:
+    what the unquantized step runs); and the skinny kernel looped over 16-row slices (``fp8_loop``)."""
+    from ..ops import gemm
+    from ..ops.skinny import _mm_nt_fp32
+
+    dev, dt = "cuda", torch.bfloat16
+    torch.manual_seed(0)
+    x = torch.randn(M, K, device=dev, dtype=dt)
+    w = torch.randn(N, K, device=dev, dtype=dt) * K**-0.5
+    out = torch.empty(M, N, device=dev, dtype=dt)
+    w8, s8 = ops.quantize_fp8_rows(w)
+    w4, s4 = ops.quantize_mxfp4_rows(w)
+    assert gemm.wq_w8_ok(x, w8, s8) and gemm.wq_w4_ok(x, w4, s4)
+    nbytes = dict(fp8=float(w8.numel() + 4 * s8.numel()), fp4=float(w4.numel() + s4.numel()), mm=float(2 * w.numel()))
+    rw, kg, tn = torch.ops.cs336.gemm_wq_plan(False, M, N, K)
+    row = dict(model=model_size, proj=name, M=M, N=N, K=K, dtype="bf16", fp8_plan=[rw, kg, tn],
+               fp4_plan=list(torch.ops.cs336.gemm_wq_plan(True, M, N, K)))
+
+    def loop():
+        for i in range(0, M, 16):
+            torch.ops.cs336.gemm_skinny_w8(x[i:i + 16], w8, s8, out[i:i + 16])
+
+    arms = dict(
+        fp8=lambda: torch.ops.cs336.gemm_wq_w8(x, w8, s8, out),
+        fp4=lambda: torch.ops.cs336.gemm_wq_w4(x, w4, s4, out),
+        fp8_old=lambda: (_mm_nt_fp32(x, w8.to(dt)) * s8).to(dt),
+        fp4_old=lambda: _mm_nt_fp32(x, ops.dequantize_mxfp4_rows(w4, s4, dt)).to(dt),
+        mm=lambda: torch.mm(x, w.t()),
+        fp8_loop=loop,
+    )
+    for k, (med, lo, hi) in _alternating(arms, warmup, rep).items():
+        row[f"{k}_us"], row[f"{k}_us_q20"], row[f"{k}_us_q80"] = med, lo, hi
+    for k in ("fp8", "fp4"):
+        row[f"{k}_gbs"] = nbytes[k] / (row[f"{k}_us"] * 1e-6) / 1e9
+        row[f"{k}_hbm_frac"] = row[f"{k}_gbs"] / HBM_ACHIEVABLE_GBS
+        row[f"{k}_vs_old"] = _verdict(row, k, f"{k}_old")
+        row[f"{k}_vs_mm"] = _verdict(row, k, "mm")
+    row["mm_gbs"] = nbytes["mm"] / (row["mm_us"] * 1e-6) / 1e9
+    row["fp8_vs_loop"] = _verdict(row, "fp8", "fp8_loop")
+    torch.ops.cs336.gemm_wq_w8(x, w8, s8, out)
+    row["fp8_max_abs_diff_vs_ref"] = (out.float() - ops.skinny_linear_fp8_ref(x, w8, s8).float()).abs().max().item()
+    torch.ops.cs336.gemm_wq_w4(x, w4, s4, out)
+    row["fp4_max_abs_diff_vs_ref"] = (out.float() - ops.skinny_linear_mxfp4_ref(x, w4, s4).float()).abs().max().item()
+    del x, w, out, w8, s8, w4, s4
+    torch.cuda.empty_cache()
+    return row
+
+
+def wq_step_rows(model_size: str = "xl", rep: int = 30) -> list[dict]:
+    """The replayed step with quantized weights where its projections have 17..128 rows: the 16-token verify
+    step at B 8 on 4096 cached tokens (M = 128) and the one-token step at B 64 on 512. Graphs on one cache,
+    interleaved as in ``verify_step_rows``: bf16 weights, and per format the step as routed now (``fp8`` /
+    ``fp4``) and with the 17..128-row kernel switched off while the graph is captured (``fp8_old`` /
+    ``fp4_old``: the dequantize + hipBLASLt path those rows took before)."""
+    from unittest import mock
+
+    from ..models import DecodeGraph, Fp8DecodeWeights, Mxfp4DecodeWeights, build_model
+    from ..models.kv_cache import KVCache
+    from ..ops import gemm
+
+    rows = []
+    for B, n, cached in ((8, 16, 4096), (64, 1, 512)):
+        torch.manual_seed(0)
+        model = build_model(model_size, cached + n, device="cuda").to(torch.bfloat16).eval()
+        x = torch.randint(0, model.vocab_size, (B, cached + n), device="cuda")
+        cache = KVCache(model, B)
+        for i in range(0, cached, 1024):  # prefill in pieces: bounded activations
+            (model.extend_cached if i else model.forward_cached)(x[:, i:i + 1024], cache)
+        kw = dict(capture=True, tokens=n, verify=True) if n > 1 else dict(capture=True)
+        graphs = {"bf16": DecodeGraph(model, cache, **kw)}
+        for key, cls in (("fp8", Fp8DecodeWeights), ("fp4", Mxfp4DecodeWeights)):
+            qw = cls(model)
+            graphs[key] = DecodeGraph(model, cache, weights=qw, **kw)
+            if key == "fp8":
+                with mock.patch.object(gemm, "wq_w8_ok", lambda *a: False):
+                    graphs["fp8_old"] = DecodeGraph(model, cache, weights=qw, **kw)
+        cache.truncate(cached)
+        times = {key: [] for key in graphs}
+        for r in range(rep + 5):
+            for key, dg in graphs.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                dg.step(x[:, cached:cached + n])
+                b.record()
+                b.synchronize()
+                cache.truncate(cached)
+                if r >= 5:  # the first rounds warm clocks and caches
+                    times[key].append(a.elapsed_time(b) * 1e3)
+        row = dict(model=model_size, B=B, tokens=n, cached=cached, M=B * n)
+        for key, ts in times.items():
+            ts = sorted(ts)
+            row[f"{key}_us"], row[f"{key}_us_q20"], row[f"{key}_us_q80"] = ts[len(ts) // 2], ts[len(ts) // 5], ts[len(ts) * 4 // 5]
+        row["fp8_vs_old"] = _verdict(row, "fp8", "fp8_old")
+        for key in ("fp8", "fp4"):
+            row[f"{key}_vs_bf16"] = _verdict(row, key, "bf16")
+        rows.append(row)
+        del graphs, cache, model
+        torch.cuda.empty_cache()
+    return rows
+
+
 SAMPLE_B, SAMPLE_V, SAMPLE_K = (1, 8, 64), (10000, 50257), (1, 50, None)
 
 
@@ -775,6 +883,8 @@ def main(argv=None):
     ap.add_argument("--skinny", action="store_true", help="the skinny-M GEMM table (xl and 2.7b projections)")
     ap.add_argument("--fp8", action="store_true", help="with --skinny: add the FP8 weight-only kernel to every row")
     ap.add_argument("--fp4", action="store_true", help="with --skinny: add the MXFP4 weight-only kernel to every row")
+    ap.add_argument("--wq", action="store_true",
+                    help="with --skinny: instead, the 17..128-row weight-only GEMM table (M 32 / 64 / 128) and the replayed steps")
     ap.add_argument("--kv-fp8", action="store_true",
                     help="add the FP8 KV cache kernels to every kernel / chunk row, and the end-to-end point "
                          "context 4096, B 8, prompt 2048 + 512")
@@ -896,7 +1006,18 @@ def main(argv=None):
                                    paged=tuple(a.page_size) if a.paged else ())
                     out["kernel"].append(r)
                     print(json.dumps(r), flush=True)
-    if a.skinny:
+    if a.skinny and a.wq:
+        out["wq"] = []
+        for size in ("xl", "2.7b"):
+            for name, N, K in skinny_shapes(size):
+                for M in WQ_M:
+                    r = wq_row(size, name, M, N, K, rep=a.rep)
+                    out["wq"].append(r)
+                    print(json.dumps(r), flush=True)
+        out["wq_step"] = wq_step_rows(a.model, rep=a.rep)
+        for r in out["wq_step"]:
+            print(json.dumps(r), flush=True)
+    elif a.skinny:
         for size in ("xl", "2.7b"):
             for name, N, K in skinny_shapes(size):
                 for M in SKINNY_M:

@@ -277,6 +277,16 @@ if hasattr(torch.ops.cs336, "gemm_skinny"):  # (absent from libraries built befo
         def _gemm_skinny_w4(x, wq, scale, out):
             return None
 
+    if hasattr(torch.ops.cs336, "gemm_wq_w8"):  # (absent from libraries built before the 17..128-row kernel)
+
+        @register_fake("cs336::gemm_wq_w8")
+        def _gemm_wq_w8(x, wq, scale, out):
+            return None
+
+        @register_fake("cs336::gemm_wq_w4")
+        def _gemm_wq_w4(x, wq, scale, out):
+            return None
+
 
 if hasattr(torch.ops.cs336, "sample_logits"):  # (absent from libraries built before the fused sampler: A/B baselines)
 

@@ -405,6 +405,62 @@ def skinny_w8_mm(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torc
     return out
 
 
+WQ_MAX_M = 128  # most rows of the weight-only FP8 / MXFP4 GEMM for SKINNY_MAX_M < M (csrc/gemm/gemm_wq.hip)
+
+
+def _as_rows(x: torch.Tensor, rows: int) -> torch.Tensor:
+    """An empty stand-in with ``rows`` rows and ``x``'s other properties that the skinny predicates look at."""
+    return x.as_strided((rows, x.shape[1]), (0, 1)) if x.dim() == 2 and x.shape[1] else x
+
+
+def wq_w8_ok(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> bool:
+    """Whether ``cs336::gemm_wq_w8`` takes ``(x @ wq.T) * scale``: 17 to ``WQ_MAX_M`` rows, and otherwise
+    the operand rules of :func:`skinny_w8_ok` (K % 16 == 0, row-major, 16-B aligned rows, ``wq`` rows at
+    least K apart, any non-negative ``x`` row stride)."""
+    return (
+        x.dim() == 2
+        and SKINNY_MAX_M < x.shape[0] <= WQ_MAX_M
+        and x.stride(0) >= 0
+        and _aligned_rows(x)
+        and skinny_w8_ok(_as_rows(x, 1), wq, scale)
+        and ops().gemm_wq_w8_ok(x.shape[0], wq.shape[0], x.shape[1], x.element_size())
+    )
+
+
+def wq_w8_routed(m: int, n: int, k: int) -> bool:
+    """FP8 shapes ``ops.skinny_linear_fp8`` sends to the 17..128-row kernel: all but long-K, short-N weights
+    above 32 rows, where the kernel has too few workgroups and stays slower than dequantize + hipBLASLt
+    (``profiles/decode_wq.md``: xl W2, 1600 x 6400, 82.8 us against 65.4 at M 64 and 66.4 against 60.9 at
+    M 128; 2.7b W2, 2560 x 10240, 133.1 against 117.8 at M 64). MXFP4 has no exception: its earlier path is
+    slower on every measured row."""
+    return not (m > 32 and k >= 4 * n)
+
+
+def wq_w8_mm(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    out = torch.empty(x.shape[0], wq.shape[0], device=x.device, dtype=x.dtype)
+    ops().gemm_wq_w8(x, wq, scale, out)
+    return out
+
+
+def wq_w4_ok(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> bool:
+    """Whether ``cs336::gemm_wq_w4`` takes ``x @ dq.T``: 17 to ``WQ_MAX_M`` rows, and otherwise the operand
+    rules of :func:`skinny_w4_ok` (K % 32 == 0, 16-B aligned rows, padded ``wq`` / ``scale`` rows allowed)."""
+    return (
+        x.dim() == 2
+        and SKINNY_MAX_M < x.shape[0] <= WQ_MAX_M
+        and x.stride(0) >= 0
+        and _aligned_rows(x)
+        and skinny_w4_ok(_as_rows(x, 1), wq, scale)
+        and ops().gemm_wq_w4_ok(x.shape[0], wq.shape[0], x.shape[1], x.element_size())
+    )
+
+
+def wq_w4_mm(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    out = torch.empty(x.shape[0], wq.shape[0], device=x.device, dtype=x.dtype)
+    ops().gemm_wq_w4(x, wq, scale, out)
+    return out
+
+
 def skinny_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
     """Whether ``cs336::gemm_skinny`` takes ``x @ w.T``: GPU bf16 / fp16 of one dtype, at most 16
     rows, K % 8 == 0, row-major operands with 16-B aligned rows (``w`` rows at least K apart)."""

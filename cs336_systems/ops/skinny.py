@@ -12,7 +12,9 @@ FP8 weights (weight-only, W8A16). ``quantize_fp8_rows(w)`` gives ``(wq, scale)``
 ``wq[n, k] * scale[n]``. ``skinny_linear_fp8(x, wq, scale)`` is ``(x @ wq.T) * scale`` with the
 activations left in 16 bits: on a GPU, at most 16 rows run the e4m3 format of
 ``csrc/gemm/gemm_skinny.hip``, which streams half the bytes of the 16-bit format, converts W in registers (exactly) and applies the scale
-to the fp32 sum before its one rounding.
+to the fp32 sum before its one rounding. 17 to 128 rows (batched decode, verify and chunk steps) run
+``csrc/gemm/gemm_wq.hip`` in either quantized format: the same bytes and the same contract, with x
+staged through LDS for up to 8 MFMA tiles of batch rows.
 
 MXFP4 weights (weight-only, W4A16). ``quantize_mxfp4_rows(w)`` gives ``(wq, scale)`` in the OCP
 microscaling format: ``wq`` (N, K/2) uint8 with two e2m1 codes per byte (k = 2j in bits 3:0, k = 2j+1 in
@@ -111,7 +113,10 @@ def skinny_linear_fp8(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) ->
 
     On a GPU with the HIP backend, at most 16 rows in total that ``gemm.skinny_w8_ok`` takes (K % 16
     == 0, 16-B aligned rows) run the FP8 weight-streaming kernel: fp32 accumulation, the scale applied
-    to the fp32 sum, one rounding. More than 16 rows run the existing GEMM (hipBLASLt) on
+    to the fp32 sum, one rounding. 17 to 128 rows that ``gemm.wq_w8_ok`` takes (the same operand rules)
+    run the weight-only GEMM of ``csrc/gemm/gemm_wq.hip`` under the same contract: W streamed and
+    converted once, x shared through LDS (``gemm.wq_w8_routed`` keeps the measured exception, long-K
+    short-N weights above 32 rows, on the next path). More than 128 rows run the existing GEMM (hipBLASLt) on
     ``wq.to(x.dtype)``, an exact conversion, with an fp32 result, then the scale in fp32 and one
     rounding. Through ``gemm.mm_nt``'s 16-bit output that path would round twice, once to the GEMM
     output and once after the scale, and be off by up to a whole ulp of the output, which the tests'
@@ -124,6 +129,8 @@ def skinny_linear_fp8(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) ->
     x2 = x.reshape(-1, x.shape[-1])
     if x2.shape[0] <= gemm.SKINNY_MAX_M and gemm.skinny_w8_ok(x2, wq, scale):
         y = gemm.skinny_w8_mm(x2, wq, scale)
+    elif gemm.wq_w8_routed(x2.shape[0], wq.shape[0], x2.shape[1]) and gemm.wq_w8_ok(x2, wq, scale):
+        y = gemm.wq_w8_mm(x2, wq, scale)
     elif x2.shape[0] > gemm.SKINNY_MAX_M and x2.dtype in (torch.bfloat16, torch.float16):
         y = (_mm_nt_fp32(x2, wq.to(x2.dtype)) * scale).to(x2.dtype)
     else:
@@ -237,8 +244,9 @@ def skinny_linear_mxfp4(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) 
     accepted).
 
     On a GPU with the HIP backend, at most 16 rows in total that ``gemm.skinny_w4_ok`` takes (16-B
-    aligned rows) run the MXFP4 weight-streaming kernel: fp32 accumulation, one rounding. More than 16
-    rows run the existing GEMM on the dequantized weight in ``x``'s dtype (an exact conversion) with an
+    aligned rows) run the MXFP4 weight-streaming kernel: fp32 accumulation, one rounding. 17 to 128 rows
+    that ``gemm.wq_w4_ok`` takes run the weight-only GEMM of ``csrc/gemm/gemm_wq.hip`` under the same
+    contract. More than 128 rows run the existing GEMM on the dequantized weight in ``x``'s dtype (an exact conversion) with an
     fp32 result, rounded once. Anything else on the GPU, and the CPU, runs
     :func:`skinny_linear_mxfp4_ref`. A missing extension on a HIP-backend GPU raises."""
     if not use_hip(x, wq):
@@ -246,6 +254,8 @@ def skinny_linear_mxfp4(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) 
     x2 = x.reshape(-1, x.shape[-1])
     if x2.shape[0] <= gemm.SKINNY_MAX_M and gemm.skinny_w4_ok(x2, wq, scale):
         y = gemm.skinny_w4_mm(x2, wq, scale)
+    elif gemm.wq_w4_ok(x2, wq, scale):
+        y = gemm.wq_w4_mm(x2, wq, scale)
     elif x2.shape[0] > gemm.SKINNY_MAX_M and x2.dtype in (torch.bfloat16, torch.float16):
         y = _mm_nt_fp32(x2, dequantize_mxfp4_rows(wq, scale, x2.dtype)).to(x2.dtype)
     else:

@@ -20,6 +20,7 @@
 #include "cs336/kernels.h"
 #include "../gemm/gemm8.h"
 #include "../gemm/skinny_plan.h"
+#include "../gemm/gemm_wq_plan.h"
 
 namespace {
 
@@ -2201,8 +2202,9 @@ bool gemm_skinny_w4_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
 // What the three ops check and fill alike; w's dtype (and scale) is the caller's. `op` and `wn` name the
 // op and its weight operand in the messages; kl is the format's k per 16-byte W load, wl the elements of
 // w's storage in one (MXFP4 packs two k per byte).
+// wq: the 17..128-row ops (gemm_wq_*), which differ in the rows they take and nothing else.
 static cs336::SkinnyParams skinny_params(const char* op, const char* wn, cs336::SkinnyFormat f, const at::Tensor& x,
-                                         const at::Tensor& w, at::Tensor& out) {
+                                         const at::Tensor& w, at::Tensor& out, bool wq = false) {
   const int64_t kl = cs336::skinny_k_per_load(f);
   const int64_t kpw = f == cs336::SkinnyFormat::MXFP4 ? 2 : 1, wl = kl / kpw;
   check_cuda(x, "x");
@@ -2214,9 +2216,11 @@ static cs336::SkinnyParams skinny_params(const char* op, const char* wn, cs336::
   TORCH_CHECK(w.device() == x.device() && out.device() == x.device(), "cs336: ", op, " tensors must be on one device");
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) * kpw == K && out.size(0) == M && out.size(1) == N, "cs336: ", op, " shape mismatch");
-  TORCH_CHECK(M >= 1 && M <= 16, "cs336: ", op, " takes 1 <= M <= 16 (got ", M, ")");
+  const int64_t m_lo = wq ? cs336::kWqMinM : 1, m_hi = wq ? cs336::kWqMaxM : 16;
+  TORCH_CHECK(M >= m_lo && M <= m_hi, "cs336: ", op, " takes ", m_lo, " <= M <= ", m_hi, " (got ", M, ")");
   TORCH_CHECK(K >= kl && K % kl == 0, "cs336: ", op, " needs K % ", kl, " == 0 (got ", K, ")");
-  TORCH_CHECK(cs336::gemm_skinny_ok(f, M, N, K, x.element_size()), "cs336: ", op, " extents exceed the kernel's 32-bit row / k indices");
+  TORCH_CHECK(wq ? cs336::gemm_wq_ok(f, M, N, K, x.element_size()) : cs336::gemm_skinny_ok(f, M, N, K, x.element_size()), "cs336: ", op,
+              " extents exceed the kernel's 32-bit row / k indices");
   TORCH_CHECK(x.stride(1) == 1 && w.stride(1) == 1 && out.stride(1) == 1, "cs336: ", op, " operands must have a contiguous last dim");
   TORCH_CHECK(x.stride(0) % 8 == 0 && (M == 1 || x.stride(0) >= 0), "cs336: ", op, " x row stride must be a non-negative multiple of 8");
   TORCH_CHECK(w.stride(0) % wl == 0 && (N == 1 || w.stride(0) >= K / kpw), "cs336: ", op, " ", wn, " row stride must be a multiple of ", wl,
@@ -2245,34 +2249,63 @@ void gemm_skinny(const at::Tensor& x, const at::Tensor& w, at::Tensor& out) {
   cs336::gemm_skinny(p, cs336::SkinnyFormat::W16, to_dtype(x), stream());
 }
 
-void gemm_skinny_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
+static void w8_op(const char* op, bool wide, const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
   check_cuda(scale, "scale");
-  TORCH_CHECK(scale.dim() == 1, "cs336: gemm_skinny_w8 takes x (M, K), wq (N, K), scale (N,), out (M, N)");
+  TORCH_CHECK(scale.dim() == 1, "cs336: ", op, " takes x (M, K), wq (N, K), scale (N,), out (M, N)");
   TORCH_CHECK(wq.scalar_type() == at::kFloat8_e4m3fn || wq.scalar_type() == at::kByte,
-              "cs336: gemm_skinny_w8 takes wq as float8_e4m3fn or its uint8 view");
-  TORCH_CHECK(scale.scalar_type() == at::kFloat, "cs336: gemm_skinny_w8 scale must be fp32");
-  TORCH_CHECK(scale.device() == x.device(), "cs336: gemm_skinny_w8 tensors must be on one device");
-  cs336::SkinnyParams p = skinny_params("gemm_skinny_w8", "wq", cs336::SkinnyFormat::E4M3, x, wq, out);
-  TORCH_CHECK(scale.size(0) == p.N && scale.is_contiguous(), "cs336: gemm_skinny_w8 scale must be contiguous with N = ", p.N, " elements");
+              "cs336: ", op, " takes wq as float8_e4m3fn or its uint8 view");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat, "cs336: ", op, " scale must be fp32");
+  TORCH_CHECK(scale.device() == x.device(), "cs336: ", op, " tensors must be on one device");
+  cs336::SkinnyParams p = skinny_params(op, "wq", cs336::SkinnyFormat::E4M3, x, wq, out, wide);
+  TORCH_CHECK(scale.size(0) == p.N && scale.is_contiguous(), "cs336: ", op, " scale must be contiguous with N = ", p.N, " elements");
   p.scale = scale.data_ptr<float>();
   c10::DeviceGuard g(x.device());
-  cs336::gemm_skinny(p, cs336::SkinnyFormat::E4M3, to_dtype(x), stream());
+  (wide ? cs336::gemm_wq : cs336::gemm_skinny)(p, cs336::SkinnyFormat::E4M3, to_dtype(x), stream());
 }
 
-void gemm_skinny_w4(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
+static void w4_op(const char* op, bool wide, const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
   check_cuda(scale, "scale");
-  TORCH_CHECK(scale.dim() == 2, "cs336: gemm_skinny_w4 takes x (M, K), wq (N, K/2), scale (N, K/32), out (M, N)");
-  TORCH_CHECK(wq.scalar_type() == at::kByte || wq.scalar_type() == at::ScalarType::Float4_e2m1fn_x2, "cs336: gemm_skinny_w4 takes wq as uint8 or float4_e2m1fn_x2");
-  TORCH_CHECK(scale.scalar_type() == at::kByte || scale.scalar_type() == at::ScalarType::Float8_e8m0fnu, "cs336: gemm_skinny_w4 takes scale as uint8 or float8_e8m0fnu");
-  TORCH_CHECK(scale.device() == x.device(), "cs336: gemm_skinny_w4 tensors must be on one device");
-  cs336::SkinnyParams p = skinny_params("gemm_skinny_w4", "wq", cs336::SkinnyFormat::MXFP4, x, wq, out);
-  TORCH_CHECK(scale.size(0) == p.N && scale.size(1) == p.K / 32, "cs336: gemm_skinny_w4 scale must be (N, K/32) = (", p.N, ", ", p.K / 32, ")");
+  TORCH_CHECK(scale.dim() == 2, "cs336: ", op, " takes x (M, K), wq (N, K/2), scale (N, K/32), out (M, N)");
+  TORCH_CHECK(wq.scalar_type() == at::kByte || wq.scalar_type() == at::ScalarType::Float4_e2m1fn_x2, "cs336: ", op, " takes wq as uint8 or float4_e2m1fn_x2");
+  TORCH_CHECK(scale.scalar_type() == at::kByte || scale.scalar_type() == at::ScalarType::Float8_e8m0fnu, "cs336: ", op, " takes scale as uint8 or float8_e8m0fnu");
+  TORCH_CHECK(scale.device() == x.device(), "cs336: ", op, " tensors must be on one device");
+  cs336::SkinnyParams p = skinny_params(op, "wq", cs336::SkinnyFormat::MXFP4, x, wq, out, wide);
+  TORCH_CHECK(scale.size(0) == p.N && scale.size(1) == p.K / 32, "cs336: ", op, " scale must be (N, K/32) = (", p.N, ", ", p.K / 32, ")");
   TORCH_CHECK(scale.stride(1) == 1 && (p.N == 1 || scale.stride(0) >= p.K / 32),
-              "cs336: gemm_skinny_w4 scale needs a contiguous last dim and rows at least K/32 apart");
+              "cs336: ", op, " scale needs a contiguous last dim and rows at least K/32 apart");
   p.bscale = static_cast<const uint8_t*>(scale.data_ptr());
   p.ldbs = p.N == 1 ? 0 : scale.stride(0);
   c10::DeviceGuard g(x.device());
-  cs336::gemm_skinny(p, cs336::SkinnyFormat::MXFP4, to_dtype(x), stream());
+  (wide ? cs336::gemm_wq : cs336::gemm_skinny)(p, cs336::SkinnyFormat::MXFP4, to_dtype(x), stream());
+}
+
+void gemm_skinny_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
+  w8_op("gemm_skinny_w8", false, x, wq, scale, out);
+}
+void gemm_skinny_w4(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
+  w4_op("gemm_skinny_w4", false, x, wq, scale, out);
+}
+
+// The same two products for 17 <= M <= 128 rows (csrc/gemm/gemm_wq.hip): operands and checks as above.
+// gemm_wq_plan: the (RW, KG, TN) the launch for (M, N, K) uses; w4: the MXFP4 format, else e4m3.
+void gemm_wq_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
+  w8_op("gemm_wq_w8", true, x, wq, scale, out);
+}
+void gemm_wq_w4(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
+  w4_op("gemm_wq_w4", true, x, wq, scale, out);
+}
+bool gemm_wq_w8_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
+  return cs336::gemm_wq_ok(cs336::SkinnyFormat::E4M3, M, N, K, elem_size);
+}
+bool gemm_wq_w4_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
+  return cs336::gemm_wq_ok(cs336::SkinnyFormat::MXFP4, M, N, K, elem_size);
+}
+std::vector<int64_t> gemm_wq_plan(bool w4, int64_t M, int64_t N, int64_t K) {
+  const cs336::SkinnyFormat f = w4 ? cs336::SkinnyFormat::MXFP4 : cs336::SkinnyFormat::E4M3;
+  TORCH_CHECK(cs336::gemm_wq_ok(f, M, N, K, 2), "cs336: gemm_wq_plan takes shapes the kernel takes");
+  int rw, kg, tn;
+  cs336::gemm_wq_plan(f, (int)M, (int)N, (int)K, rw, kg, tn);
+  return {rw, kg, tn};
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2361,6 +2394,11 @@ TORCH_LIBRARY(cs336, m) {
   m.def("gemm_skinny_w8_ok(int M, int N, int K, int elem_size) -> bool", &gemm_skinny_w8_ok);
   m.def("gemm_skinny_w4(Tensor x, Tensor wq, Tensor scale, Tensor(a!) out) -> ()");
   m.def("gemm_skinny_w4_ok(int M, int N, int K, int elem_size) -> bool", &gemm_skinny_w4_ok);
+  m.def("gemm_wq_w8(Tensor x, Tensor wq, Tensor scale, Tensor(a!) out) -> ()");
+  m.def("gemm_wq_w8_ok(int M, int N, int K, int elem_size) -> bool", &gemm_wq_w8_ok);
+  m.def("gemm_wq_w4(Tensor x, Tensor wq, Tensor scale, Tensor(a!) out) -> ()");
+  m.def("gemm_wq_w4_ok(int M, int N, int K, int elem_size) -> bool", &gemm_wq_w4_ok);
+  m.def("gemm_wq_plan(bool w4, int M, int N, int K) -> int[]", &gemm_wq_plan);
   m.def("gemm_skinny(Tensor x, Tensor w, Tensor(a!) out) -> ()");
   m.def("gemm_skinny_ok(int M, int N, int K, int elem_size) -> bool", &gemm_skinny_ok);
   m.def(
@@ -2480,6 +2518,8 @@ TORCH_LIBRARY_IMPL(cs336, CUDA, m) {
   m.impl("sample_advance", &sample_advance);
   m.impl("gemm_skinny_w8", &gemm_skinny_w8);
   m.impl("gemm_skinny_w4", &gemm_skinny_w4);
+  m.impl("gemm_wq_w8", &gemm_wq_w8);
+  m.impl("gemm_wq_w4", &gemm_wq_w4);
   m.impl("gemm_skinny", &gemm_skinny);
   m.impl("fa_decode", &fa_decode);
   m.impl("kv_append_rope", &kv_append_rope);

@@ -491,6 +491,12 @@ bool gemm_skinny_ok(SkinnyFormat f, int64_t M, int64_t N, int64_t K, int64_t ele
 void gemm_skinny(const SkinnyParams& p, SkinnyFormat f, DType t, hipStream_t s);
 void gemm_skinny_w4(const SkinnyParams& p, DType t, hipStream_t s);  // the MXFP4 format; gemm_skinny forwards to it
 
+// ---- weight-only FP8 / MXFP4 GEMM for 17 <= M <= 128 (csrc/gemm/gemm_wq.hip) ----
+// The E4M3 and MXFP4 products above with the same SkinnyParams and operand rules, for 17..128 rows: W
+// streamed and converted once, x staged through LDS, launch plan in csrc/gemm/gemm_wq_plan.h.
+bool gemm_wq_ok(SkinnyFormat f, int64_t M, int64_t N, int64_t K, int64_t elem_size);
+void gemm_wq(const SkinnyParams& p, SkinnyFormat f, DType t, hipStream_t s);
+
 // ---- temperature / top-k sampler (csrc/ops/sample.hip) ----
 // One token per row of logits (B, V; bf16 / fp16 / fp32 (DType), contiguous last dim, any element-aligned
 // row stride >= 0, 1 <= V <= 2^30) from one caller-supplied uniform u in [0, 1) per row; the rule is in
