@@ -103,6 +103,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import os
 import time
 
 import torch
@@ -702,6 +703,130 @@ def wq_step_rows(model_size: str = "xl", rep: int = 30) -> list[dict]:
     return rows
 
 
+WQT_M = (129, 256, 512, 2048)
+
+
+def wqt_row(model_size: str, name: str, M: int, N: int, K: int, warmup: int = 5, rep: int = 50) -> dict:
+    """One projection above 128 rows, the arms alternating in one run: the tile GEMM of
+    ``csrc/gemm/gemm_wqt.hip`` in both formats (``fp8``, ``fp4``); the path the same call took before it
+    (``fp8_old`` / ``fp4_old``: dequantize, hipBLASLt with an fp32 result, scale, cast -- ``ops.skinny``'s
+    ``_fp8_dequant_mm`` / ``_mxfp4_dequant_mm``); and ``torch.mm`` on the bf16 weight (``mm``)."""
+    from ..ops import gemm
+    from ..ops.skinny import _fp8_dequant_mm, _mxfp4_dequant_mm
+
+    dev, dt = "cuda", torch.bfloat16
+    torch.manual_seed(0)
+    x = torch.randn(M, K, device=dev, dtype=dt)
+    w = torch.randn(N, K, device=dev, dtype=dt) * K**-0.5
+    out = torch.empty(M, N, device=dev, dtype=dt)
+    w8, s8 = ops.quantize_fp8_rows(w)
+    w4, s4 = ops.quantize_mxfp4_rows(w)
+    assert gemm.wqt_w8_ok(x, w8, s8) and gemm.wqt_w4_ok(x, w4, s4)
+    row = dict(model=model_size, proj=name, M=M, N=N, K=K, dtype="bf16",
+               fp8_plan=list(torch.ops.cs336.gemm_wqt_plan(False, M, N, K)),
+               fp4_plan=list(torch.ops.cs336.gemm_wqt_plan(True, M, N, K)))
+    arms = dict(
+        fp8=lambda: torch.ops.cs336.gemm_wqt_w8(x, w8, s8, out),
+        fp4=lambda: torch.ops.cs336.gemm_wqt_w4(x, w4, s4, out),
+        fp8_old=lambda: _fp8_dequant_mm(x, w8, s8),
+        fp4_old=lambda: _mxfp4_dequant_mm(x, w4, s4),
+        mm=lambda: torch.mm(x, w.t()),
+    )
+    for k, (med, lo, hi) in _alternating(arms, warmup, rep).items():
+        row[f"{k}_us"], row[f"{k}_us_q20"], row[f"{k}_us_q80"] = med, lo, hi
+    for k in ("fp8", "fp4"):
+        row[f"{k}_tflops"] = 2.0 * M * N * K / (row[f"{k}_us"] * 1e-6) / 1e12
+        row[f"{k}_vs_old"] = _verdict(row, k, f"{k}_old")
+        row[f"{k}_vs_mm"] = _verdict(row, k, "mm")
+    torch.ops.cs336.gemm_wqt_w8(x, w8, s8, out)
+    row["fp8_max_abs_diff_vs_ref"] = (out.float() - ops.skinny_linear_fp8_ref(x, w8, s8).float()).abs().max().item()
+    torch.ops.cs336.gemm_wqt_w4(x, w4, s4, out)
+    row["fp4_max_abs_diff_vs_ref"] = (out.float() - ops.skinny_linear_mxfp4_ref(x, w4, s4).float()).abs().max().item()
+    del x, w, out, w8, s8, w4, s4
+    torch.cuda.empty_cache()
+    return row
+
+
+def wqt_step_rows(model_size: str = "xl", rep: int = 20) -> list[dict]:
+    """Model steps whose projections have more than 128 rows, the arms interleaved in one run: the prefill of
+    2048 tokens at B 1 on bf16 weights and with ``weights=`` in both formats (eager, a fresh cache per call),
+    and the replayed ``DecodeGraph(tokens=16, verify=True)`` at B 16 (256 rows) on 2048 cached tokens with bf16,
+    FP8 and MXFP4 weights."""
+    from ..models import DecodeGraph, Fp8DecodeWeights, Mxfp4DecodeWeights, build_model
+    from ..models.kv_cache import KVCache
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) * 1e3
+
+    def fill(row, times):
+        for key, ts in times.items():
+            ts = sorted(ts)
+            row[f"{key}_us"], row[f"{key}_us_q20"], row[f"{key}_us_q80"] = ts[len(ts) // 2], ts[len(ts) // 5], ts[len(ts) * 4 // 5]
+        for key in ("fp8", "fp4"):
+            row[f"{key}_vs_bf16"] = _verdict(row, key, "bf16")
+        return row
+
+    rows = []
+    torch.manual_seed(0)
+    P, B, n, cached = 2048, 16, 16, 2048
+    model = build_model(model_size, cached + n, device="cuda").to(torch.bfloat16).eval()
+    weights = dict(bf16=None, fp8=Fp8DecodeWeights(model), fp4=Mxfp4DecodeWeights(model))
+    x = torch.randint(0, model.vocab_size, (B, cached + n), device="cuda")
+    cache = KVCache(model, 1)
+    times = {key: [] for key in weights}
+    for r in range(rep + 3):
+        for key, qw in weights.items():
+            cache.reset()
+            t = timed(lambda: model.forward_cached(x[:1, :P], cache, weights=qw))
+            if r >= 3:
+                times[key].append(t)
+    rows.append(fill(dict(model=model_size, step="prefill", B=1, tokens=P, cached=0, M=P), times))
+    del cache
+    cache = KVCache(model, B)
+    for i in range(0, cached, 512):  # prefill in pieces: bounded activations
+        (model.extend_cached if i else model.forward_cached)(x[:, i:i + 512], cache)
+    graphs = {key: DecodeGraph(model, cache, capture=True, tokens=n, verify=True, weights=qw) for key, qw in weights.items()}
+    cache.truncate(cached)
+    times = {key: [] for key in graphs}
+    for r in range(rep + 5):
+        for key, dg in graphs.items():
+            t = timed(lambda: dg.step(x[:, cached:cached + n]))
+            cache.truncate(cached)
+            if r >= 5:
+                times[key].append(t)
+    rows.append(fill(dict(model=model_size, step="verify graph", B=B, tokens=n, cached=cached, M=B * n), times))
+    del graphs, cache, model
+    torch.cuda.empty_cache()
+    return rows
+
+
+def wqt_markdown(rows: list[dict], steps: list[dict]) -> str:
+    """``profiles/decode_wqt.md`` from the rows of ``--skinny --wqt``: median (q20-q80) us per arm."""
+    def cell(r, k):
+        return f"{r[k + '_us']:.1f} ({r[k + '_us_q20']:.1f}-{r[k + '_us_q80']:.1f})"
+
+    out = ["# Weight-only FP8 / MXFP4 GEMM above 128 rows (`python -m cs336_systems.bench.decode --skinny --wqt`)", "",
+           "Median (q20-q80) us over flushed calls, the arms alternating in one run; faster / slower only where the",
+           "q20-q80 ranges of both sides do not overlap. `old`: dequantize + hipBLASLt + scale; `mm`: `torch.mm` on the",
+           "bf16 weight. Plan: (BM, BN, splits).", "",
+           "| model | proj | M | N | K | fp8 plan | fp8 | fp8 old | fp8 vs old | fp4 | fp4 old | fp4 vs old | mm | fp8 vs mm | fp4 vs mm |",
+           "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        out.append(f"| {r['model']} | {r['proj']} | {r['M']} | {r['N']} | {r['K']} | {tuple(r['fp8_plan'])} | {cell(r, 'fp8')} | "
+                   f"{cell(r, 'fp8_old')} | {r['fp8_vs_old']} | {cell(r, 'fp4')} | {cell(r, 'fp4_old')} | {r['fp4_vs_old']} | "
+                   f"{cell(r, 'mm')} | {r['fp8_vs_mm']} | {r['fp4_vs_mm']} |")
+    out += ["", "| model | step | B | tokens | cached | bf16 | fp8 | fp8 vs bf16 | fp4 | fp4 vs bf16 |", "|---|---|---|---|---|---|---|---|---|---|"]
+    for r in steps:
+        out.append(f"| {r['model']} | {r['step']} | {r['B']} | {r['tokens']} | {r['cached']} | {cell(r, 'bf16')} | {cell(r, 'fp8')} | "
+                   f"{r['fp8_vs_bf16']} | {cell(r, 'fp4')} | {r['fp4_vs_bf16']} |")
+    return "\n".join(out) + "\n"
+
+
 SAMPLE_B, SAMPLE_V, SAMPLE_K = (1, 8, 64), (10000, 50257), (1, 50, None)
 
 
@@ -885,6 +1010,9 @@ def main(argv=None):
     ap.add_argument("--fp4", action="store_true", help="with --skinny: add the MXFP4 weight-only kernel to every row")
     ap.add_argument("--wq", action="store_true",
                     help="with --skinny: instead, the 17..128-row weight-only GEMM table (M 32 / 64 / 128) and the replayed steps")
+    ap.add_argument("--wqt", action="store_true",
+                    help="with --skinny: the weight-only FP8 / MXFP4 tile GEMM above 128 rows against its earlier path and torch.mm")
+    ap.add_argument("--wqt-m", nargs="+", type=int, default=list(WQT_M), help="rows of the --wqt table")
     ap.add_argument("--kv-fp8", action="store_true",
                     help="add the FP8 KV cache kernels to every kernel / chunk row, and the end-to-end point "
                          "context 4096, B 8, prompt 2048 + 512")
@@ -1017,6 +1145,21 @@ def main(argv=None):
         out["wq_step"] = wq_step_rows(a.model, rep=a.rep)
         for r in out["wq_step"]:
             print(json.dumps(r), flush=True)
+    elif a.skinny and a.wqt:
+        out["wqt"] = []
+        for size in ("xl", "2.7b"):
+            for name, N, K in skinny_shapes(size):
+                for M in a.wqt_m:
+                    r = wqt_row(size, name, M, N, K, rep=a.rep)
+                    out["wqt"].append(r)
+                    print(json.dumps(r), flush=True)
+        out["wqt_step"] = [] if a.no_e2e else wqt_step_rows(a.model, rep=min(a.rep, 20))
+        for r in out["wqt_step"]:
+            print(json.dumps(r), flush=True)
+        if a.json:
+            with open(os.path.splitext(a.json)[0] + ".md", "w") as f:
+                f.write(wqt_markdown(out["wqt"], out["wqt_step"]))
+        a.no_e2e = True
     elif a.skinny:
         for size in ("xl", "2.7b"):
             for name, N, K in skinny_shapes(size):

@@ -19,6 +19,7 @@ is what the CPU plumbing config of BASELINE.json exercises.
 
 from __future__ import annotations
 
+import contextlib
 import json
 import logging
 import math
@@ -672,7 +673,7 @@ class BasicsTransformerLM(nn.Module):
             return self.lm_head(y)
 
     @torch.no_grad()
-    def forward_cached(self, x: torch.Tensor, cache, chunk: bool = False) -> torch.Tensor:
+    def forward_cached(self, x: torch.Tensor, cache, chunk: bool = False, *, weights=None) -> torch.Tensor:
         """Logits ``(B, n, vocab)`` of the ``n`` tokens ``x`` that follow the ``cache.length`` tokens
         already in ``cache`` (a :class:`~cs336_systems.models.kv_cache.KVCache`); the cache then
         holds them too. On an empty cache this is the prefill (any ``n >= 1``: the ordinary forward,
@@ -690,37 +691,51 @@ class BasicsTransformerLM(nn.Module):
         ``cache`` may be a :class:`~cs336_systems.models.kv_cache.PagedKVCache`: the pages for the new
         tokens are reserved first (``cache.reserve(n)``; ``RuntimeError`` when the pool is exhausted),
         the prefill stores its rows through the block table and a step runs ``ops.kv_append_rope_paged``
-        and ``ops.decode_attention_paged``. ``chunk=True`` raises ``NotImplementedError`` on it."""
+        and ``ops.decode_attention_paged``. ``chunk=True`` raises ``NotImplementedError`` on it.
+
+        ``weights=qw`` (an ``Fp8DecodeWeights`` or ``Mxfp4DecodeWeights`` of this model): the projections read
+        the quantized copy (``gemm.skinny_decode(weights=qw)``), whatever the number of rows: the prefill
+        too then runs on 8-bit (4-bit) weights, on a GPU through ``csrc/gemm/gemm_wqt.hip`` above 128 rows."""
         start = self._cached_checks(x, cache, chunk)
         if getattr(cache, "block_table", None) is not None:
             if chunk:
                 raise NotImplementedError("forward_cached(chunk=True) is not supported on a PagedKVCache")
             cache.reserve(x.shape[1])
-        return self._forward_cached(x, cache, start)
+        with self._reading_weights(weights):
+            return self._forward_cached(x, cache, start)
+
+    @staticmethod
+    def _reading_weights(weights):
+        """The context a cached step's projections run in: ``gemm.skinny_decode(weights=...)`` for a quantized
+        copy, nothing for None."""
+        return contextlib.nullcontext() if weights is None else _gemm.skinny_decode(weights=weights)
 
     @torch.no_grad()
-    def extend_cached(self, x: torch.Tensor, cache) -> torch.Tensor:
+    def extend_cached(self, x: torch.Tensor, cache, *, weights=None) -> torch.Tensor:
         """:meth:`forward_cached` for ``n >= 1`` tokens on a cache of any length, dense or paged: a prompt
         prefilled in pieces, the next turn of a conversation, or -- on a ``PagedKVCache`` after
         ``cache.fork`` -- different (rectangular) suffixes on one shared prefix. An empty cache takes the
         ordinary prefill and ``n == 1`` the ordinary step; otherwise every layer runs the chunk append
         and ``ops.extend_attention`` (``ops.extend_attention_paged``), the MFMA kernel of
-        ``csrc/flash_attn/fa_extend.hip``. An FP8 cache raises ``NotImplementedError``."""
+        ``csrc/flash_attn/fa_extend.hip``. An FP8 cache raises ``NotImplementedError``. ``weights=``: as in
+        :meth:`forward_cached`."""
         if getattr(cache, "fp8", False):
             raise NotImplementedError("extend_cached does not support an FP8 KV cache")
         start = self._cached_checks(x, cache, True)
         if getattr(cache, "block_table", None) is not None:
             cache.reserve(x.shape[1])
-        return self._forward_cached(x, cache, start, extend=True)
+        with self._reading_weights(weights):
+            return self._forward_cached(x, cache, start, extend=True)
 
     @torch.no_grad()
-    def verify_cached(self, x: torch.Tensor, cache, *, kv_fp8: bool = False) -> torch.Tensor:
+    def verify_cached(self, x: torch.Tensor, cache, *, kv_fp8: bool = False, weights=None) -> torch.Tensor:
         """:meth:`extend_cached` on ``ops.verify_attention`` (``ops.verify_attention_paged``), the kernel of
         ``csrc/flash_attn/fa_verify.hip`` whose 16-query tile reads the cache once: the verify step of
         speculative decoding, on a dense or a paged cache. An empty cache takes the ordinary prefill and
         ``n == 1`` the ordinary step. An FP8 cache raises ``NotImplementedError`` unless ``kv_fp8=True``
         says it is meant: then ``cache`` must be a ``KVCache(fp8=True)`` (else ``ValueError``) and the step
-        appends quantized rows and attends through ``csrc/flash_attn/fa_verify_kv8.hip``."""
+        appends quantized rows and attends through ``csrc/flash_attn/fa_verify_kv8.hip``. ``weights=``: as in
+        :meth:`forward_cached`."""
         fp8 = bool(getattr(cache, "fp8", False))
         if kv_fp8 and (not fp8 or getattr(cache, "block_table", None) is not None):
             raise ValueError("verify_cached(kv_fp8=True) takes a KVCache(fp8=True)")
@@ -729,7 +744,8 @@ class BasicsTransformerLM(nn.Module):
         start = self._cached_checks(x, cache, True)
         if getattr(cache, "block_table", None) is not None:
             cache.reserve(x.shape[1])
-        return self._forward_cached(x, cache, start, verify=True)
+        with self._reading_weights(weights):
+            return self._forward_cached(x, cache, start, verify=True)
 
     def _cached_checks(self, x: torch.Tensor, cache, multi: bool) -> int:
         """The argument checks :meth:`forward_cached` and :meth:`extend_cached` share; ``multi``: whether
@@ -820,6 +836,7 @@ class BasicsTransformerLM(nn.Module):
         share_prompt: bool = False,
         prefill_chunk: int | None = None,
         verify: str = "chunk",
+        quantized_prefill: bool = False,
     ) -> torch.Tensor:
         """Autoregressive sampling (``model.py:255-310``) with a working top-k filter (the
         reference's ``masked_fill`` is not in place and its threshold broadcast is wrong for B>1).
@@ -840,6 +857,11 @@ class BasicsTransformerLM(nn.Module):
         unchanged and reads the 16-bit weights, as do the sliding-window steps once the window is
         full. With ``graph=<DecodeGraph>`` the graph's own weights are used; ``weights=`` without a
         graph raises.
+
+        ``quantized_prefill=True`` (with ``weights=qw``, else ``ValueError``): the prompt's prefill, its
+        ``prefill_chunk`` pieces included, also reads ``qw`` (:meth:`forward_cached` / :meth:`extend_cached`
+        with ``weights=qw``), so the cached part of a generation never touches the 16-bit matrices. The
+        sliding-window steps after a full window stay 16-bit.
 
         ``kv_fp8=True`` (with ``use_cache=True``): the cache is an FP8 one (``KVCache(fp8=True)``: e4m3
         rows with per-row scales, about half the bytes), and with ``draft=`` the draft's cache too. With
@@ -892,6 +914,9 @@ class BasicsTransformerLM(nn.Module):
             if draft is not None:
                 raise ValueError("generate(prefill_chunk=...) does not take draft=")
 
+        if quantized_prefill and weights is None:
+            raise ValueError("generate(quantized_prefill=True) needs weights=: the quantized copy the prefill reads")
+        pw = weights if quantized_prefill else None
         if (paged or share_prompt) and not use_cache:
             raise ValueError("generate(paged=True / share_prompt=True) needs use_cache=True")
         if paged and kv_fp8:
@@ -915,7 +940,7 @@ class BasicsTransformerLM(nn.Module):
             if not use_cache:
                 raise ValueError("generate(sample_on_device=True) needs use_cache=True")
             return self._generate_on_device(x, max_new_tokens, temperature, top_k, eos_token_id, graph, weights, kv_fp8,
-                                            generator, sync_every, paged, page_size, share_prompt, prefill_chunk)
+                                            generator, sync_every, paged, page_size, share_prompt, prefill_chunk, pw)
         if draft is not None:
             from .speculative import speculative_generate
 
@@ -960,7 +985,7 @@ class BasicsTransformerLM(nn.Module):
         for _ in range(max_new_tokens):
             ctx = x[:, -self.context_length :] if x.size(1) > self.context_length else x
             if cache is not None and cache.length == 0:
-                logits = self._prefill(ctx, cache, share_prompt, prefill_chunk)
+                logits = self._prefill(ctx, cache, share_prompt, prefill_chunk, pw)
             elif cache is not None and cache.length + 1 == x.size(1) <= self.context_length:
                 if graph is True and dg is None:
                     dg = DecodeGraph(self, cache, capture=True, weights=weights)
@@ -990,20 +1015,20 @@ class BasicsTransformerLM(nn.Module):
             return PagedKVCache(self, batch, page_size=page_size, max_len=self.context_length, device=w.device, dtype=cdt)
         return KVCache(self, batch, device=w.device, dtype=cdt, fp8=kv_fp8)
 
-    def _prefill(self, ctx, cache, share_prompt: bool, prefill_chunk: int | None = None) -> torch.Tensor:
+    def _prefill(self, ctx, cache, share_prompt: bool, prefill_chunk: int | None = None, weights=None) -> torch.Tensor:
         """The prompt's logits (B, n, vocab), whose last position the callers read (n = 1 with
         ``share_prompt``, the last piece's length with ``prefill_chunk``). With ``share_prompt`` (a paged
         cache, equal rows) row 0 alone is prefilled and forked to the others. ``prefill_chunk``: the
         prompt goes in pieces of that many tokens, the first by the prefill, the rest by
-        :meth:`extend_cached`."""
+        :meth:`extend_cached`. ``weights``: the quantized copy both read (``generate(quantized_prefill=True)``)."""
         if share_prompt:
             ctx, target = ctx[:1], cache.row(0)
         else:
             target = cache
         step = ctx.size(1) if prefill_chunk is None else int(prefill_chunk)
-        logits = self.forward_cached(ctx[:, :step], target)
+        logits = self.forward_cached(ctx[:, :step], target, weights=weights)
         for s in range(step, ctx.size(1), step):
-            logits = self.extend_cached(ctx[:, s:s + step], target)
+            logits = self.extend_cached(ctx[:, s:s + step], target, weights=weights)
         if not share_prompt:
             return logits
         cache.fork(0)
@@ -1011,7 +1036,7 @@ class BasicsTransformerLM(nn.Module):
 
     def _generate_on_device(self, x, max_new_tokens, temperature, top_k, eos_token_id, graph, weights, kv_fp8,
                             generator, sync_every, paged=False, page_size=64, share_prompt=False,
-                            prefill_chunk=None) -> torch.Tensor:
+                            prefill_chunk=None, prefill_weights=None) -> torch.Tensor:
         """``generate(sample_on_device=True)``: see there."""
         from .decode_graph import DecodeGraph, Sampler
 
@@ -1060,7 +1085,7 @@ class BasicsTransformerLM(nn.Module):
             return t[:, None], done
 
         # token 0: the prefill on the prompt's last context_length tokens
-        logits = self._prefill(x[:, -L:] if P > L else x, cache, share_prompt, prefill_chunk)
+        logits = self._prefill(x[:, -L:] if P > L else x, cache, share_prompt, prefill_chunk, prefill_weights)
         tok, done = pick(logits, 0, None)
         out = tok
         # cached steps while the sequence fits the window (and the cache)

@@ -287,6 +287,16 @@ if hasattr(torch.ops.cs336, "gemm_skinny"):  # (absent from libraries built befo
         def _gemm_wq_w4(x, wq, scale, out):
             return None
 
+    if hasattr(torch.ops.cs336, "gemm_wqt_w8"):  # (absent from libraries built before the tile GEMM above 128 rows)
+
+        @register_fake("cs336::gemm_wqt_w8")
+        def _gemm_wqt_w8(x, wq, scale, out):
+            return None
+
+        @register_fake("cs336::gemm_wqt_w4")
+        def _gemm_wqt_w4(x, wq, scale, out):
+            return None
+
 
 if hasattr(torch.ops.cs336, "sample_logits"):  # (absent from libraries built before the fused sampler: A/B baselines)
 

@@ -461,6 +461,64 @@ def wq_w4_mm(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torch.Te
     return out
 
 
+WQT_MIN_M = 129  # fewest rows of the weight-only FP8 / MXFP4 tile GEMM (csrc/gemm/gemm_wqt.hip): above WQ_MAX_M
+
+
+def wqt_w8_ok(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> bool:
+    """Whether ``cs336::gemm_wqt_w8`` takes ``(x @ wq.T) * scale``: ``WQT_MIN_M`` rows or more, and otherwise
+    the operand rules of :func:`skinny_w8_ok`."""
+    return (
+        x.dim() == 2
+        and x.shape[0] >= WQT_MIN_M
+        and x.stride(0) >= 0
+        and _aligned_rows(x)
+        and skinny_w8_ok(_as_rows(x, 1), wq, scale)
+        and ops().gemm_wqt_w8_ok(x.shape[0], wq.shape[0], x.shape[1], x.element_size())
+    )
+
+
+def wqt_w4_ok(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> bool:
+    """Whether ``cs336::gemm_wqt_w4`` takes ``x @ dq.T``: ``WQT_MIN_M`` rows or more, and otherwise the operand
+    rules of :func:`skinny_w4_ok`."""
+    return (
+        x.dim() == 2
+        and x.shape[0] >= WQT_MIN_M
+        and x.stride(0) >= 0
+        and _aligned_rows(x)
+        and skinny_w4_ok(_as_rows(x, 1), wq, scale)
+        and ops().gemm_wqt_w4_ok(x.shape[0], wq.shape[0], x.shape[1], x.element_size())
+    )
+
+
+def wqt_routed(fmt: str, m: int, n: int, k: int) -> bool:
+    """Shapes with ``WQT_MIN_M`` rows or more that ``ops.skinny_linear_fp8`` (``fmt`` ``"w8"``) and
+    ``ops.skinny_linear_mxfp4`` (``"w4"``) send to the tile GEMM of ``csrc/gemm/gemm_wqt.hip``. MXFP4: every
+    shape, since its earlier path builds its table on the host, cannot be captured and is 2 to 9 times slower on
+    every measured row. FP8: all but long-K, short-N weights (K >= 4 N: W2) at 512 rows and more, where the tile
+    count is small and dequantize + hipBLASLt stays faster (``profiles/decode_wqt.md``: 2.7b W2, 2560 x 10240,
+    188.3 us against 146.7 at M 512 and 261.0 against 198.8 at M 2048; xl W2, 1600 x 6400, 149.7 against 106.7
+    at M 2048, though 69.7 against 74.0 at M 512). The other FP8 rows are faster by 1.05 to 2.7 times, except
+    xl QKV at M 2048 (99.7 us against 97.1) and 2.7b O at M 2048 (same), which stay routed so that the prefill
+    reads one copy. Row counts other than 129, 256, 512 and 2048 were not measured."""
+    if fmt not in ("w8", "w4"):
+        raise ValueError('wqt_routed takes fmt "w8" or "w4"')
+    if fmt == "w8" and m >= 512 and k >= 4 * n:
+        return False
+    return m >= WQT_MIN_M
+
+
+def wqt_w8_mm(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    out = torch.empty(x.shape[0], wq.shape[0], device=x.device, dtype=x.dtype)
+    ops().gemm_wqt_w8(x, wq, scale, out)
+    return out
+
+
+def wqt_w4_mm(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    out = torch.empty(x.shape[0], wq.shape[0], device=x.device, dtype=x.dtype)
+    ops().gemm_wqt_w4(x, wq, scale, out)
+    return out
+
+
 def skinny_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
     """Whether ``cs336::gemm_skinny`` takes ``x @ w.T``: GPU bf16 / fp16 of one dtype, at most 16
     rows, K % 8 == 0, row-major operands with 16-B aligned rows (``w`` rows at least K apart)."""

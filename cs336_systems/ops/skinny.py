@@ -107,6 +107,17 @@ def _mm_nt_fp32(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
         return gemm.mm_nt(x, w).float()
 
 
+def _fp8_dequant_mm(x2: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """The GEMM on ``wq.to(x2.dtype)`` (exact) with an fp32 result, then the scale in fp32 and one rounding:
+    what rows the weight-only kernels do not take run, and the benchmark's baseline arm."""
+    return (_mm_nt_fp32(x2, wq.to(x2.dtype)) * scale).to(x2.dtype)
+
+
+def _mxfp4_dequant_mm(x2: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """The GEMM on the dequantized weight in ``x2``'s dtype (exact) with an fp32 result, rounded once."""
+    return _mm_nt_fp32(x2, dequantize_mxfp4_rows(wq, scale, x2.dtype)).to(x2.dtype)
+
+
 def skinny_linear_fp8(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     """``(x @ wq.T) * scale`` for ``x`` (..., K) in bf16 / fp16, ``wq`` (N, K) e4m3 (or its uint8
     view) and ``scale`` (N,) fp32 (:func:`quantize_fp8_rows`).
@@ -116,7 +127,10 @@ def skinny_linear_fp8(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) ->
     to the fp32 sum, one rounding. 17 to 128 rows that ``gemm.wq_w8_ok`` takes (the same operand rules)
     run the weight-only GEMM of ``csrc/gemm/gemm_wq.hip`` under the same contract: W streamed and
     converted once, x shared through LDS (``gemm.wq_w8_routed`` keeps the measured exception, long-K
-    short-N weights above 32 rows, on the next path). More than 128 rows run the existing GEMM (hipBLASLt) on
+    short-N weights above 32 rows, on the last path). More than 128 rows that ``gemm.wqt_w8_ok`` takes and
+    ``gemm.wqt_routed`` routes run the tile GEMM of ``csrc/gemm/gemm_wqt.hip``, again under that contract: W
+    converted once on its way into LDS, so the prefill, chunk and verify steps read the quantized copy.
+    What is left runs the existing GEMM (hipBLASLt) on
     ``wq.to(x.dtype)``, an exact conversion, with an fp32 result, then the scale in fp32 and one
     rounding. Through ``gemm.mm_nt``'s 16-bit output that path would round twice, once to the GEMM
     output and once after the scale, and be off by up to a whole ulp of the output, which the tests'
@@ -131,8 +145,10 @@ def skinny_linear_fp8(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) ->
         y = gemm.skinny_w8_mm(x2, wq, scale)
     elif gemm.wq_w8_routed(x2.shape[0], wq.shape[0], x2.shape[1]) and gemm.wq_w8_ok(x2, wq, scale):
         y = gemm.wq_w8_mm(x2, wq, scale)
+    elif gemm.wqt_routed("w8", x2.shape[0], wq.shape[0], x2.shape[1]) and gemm.wqt_w8_ok(x2, wq, scale):
+        y = gemm.wqt_w8_mm(x2, wq, scale)
     elif x2.shape[0] > gemm.SKINNY_MAX_M and x2.dtype in (torch.bfloat16, torch.float16):
-        y = (_mm_nt_fp32(x2, wq.to(x2.dtype)) * scale).to(x2.dtype)
+        y = _fp8_dequant_mm(x2, wq, scale)
     else:
         y = skinny_linear_fp8_ref(x2, wq, scale)
     return y.view(*x.shape[:-1], wq.shape[0])
@@ -246,8 +262,11 @@ def skinny_linear_mxfp4(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) 
     On a GPU with the HIP backend, at most 16 rows in total that ``gemm.skinny_w4_ok`` takes (16-B
     aligned rows) run the MXFP4 weight-streaming kernel: fp32 accumulation, one rounding. 17 to 128 rows
     that ``gemm.wq_w4_ok`` takes run the weight-only GEMM of ``csrc/gemm/gemm_wq.hip`` under the same
-    contract. More than 128 rows run the existing GEMM on the dequantized weight in ``x``'s dtype (an exact conversion) with an
-    fp32 result, rounded once. Anything else on the GPU, and the CPU, runs
+    contract, and more than 128 rows that ``gemm.wqt_w4_ok`` takes the tile GEMM of
+    ``csrc/gemm/gemm_wqt.hip`` (every such shape: ``gemm.wqt_routed``), which like the two above can be
+    captured into a HIP graph. What is left (rows the kernels do not take) runs the existing GEMM on the
+    dequantized weight in ``x``'s dtype (an exact conversion) with an fp32 result, rounded once; its table is
+    built on the host. Anything else on the GPU, and the CPU, runs
     :func:`skinny_linear_mxfp4_ref`. A missing extension on a HIP-backend GPU raises."""
     if not use_hip(x, wq):
         return skinny_linear_mxfp4_ref(x, wq, scale)
@@ -256,8 +275,10 @@ def skinny_linear_mxfp4(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) 
         y = gemm.skinny_w4_mm(x2, wq, scale)
     elif gemm.wq_w4_ok(x2, wq, scale):
         y = gemm.wq_w4_mm(x2, wq, scale)
+    elif gemm.wqt_routed("w4", x2.shape[0], wq.shape[0], x2.shape[1]) and gemm.wqt_w4_ok(x2, wq, scale):
+        y = gemm.wqt_w4_mm(x2, wq, scale)
     elif x2.shape[0] > gemm.SKINNY_MAX_M and x2.dtype in (torch.bfloat16, torch.float16):
-        y = _mm_nt_fp32(x2, dequantize_mxfp4_rows(wq, scale, x2.dtype)).to(x2.dtype)
+        y = _mxfp4_dequant_mm(x2, wq, scale)
     else:
         y = skinny_linear_mxfp4_ref(x2, wq, scale)
     return y.view(*x.shape[:-1], wq.shape[0])

@@ -21,6 +21,7 @@
 #include "../gemm/gemm8.h"
 #include "../gemm/skinny_plan.h"
 #include "../gemm/gemm_wq_plan.h"
+#include "../gemm/gemm_wqt_plan.h"
 
 namespace {
 
@@ -2202,9 +2203,10 @@ bool gemm_skinny_w4_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
 // What the three ops check and fill alike; w's dtype (and scale) is the caller's. `op` and `wn` name the
 // op and its weight operand in the messages; kl is the format's k per 16-byte W load, wl the elements of
 // w's storage in one (MXFP4 packs two k per byte).
-// wq: the 17..128-row ops (gemm_wq_*), which differ in the rows they take and nothing else.
+// wq: 0 for the skinny ops, 1 for the 17..128-row ops (gemm_wq_*), 2 for the ops above 128 rows (gemm_wqt_*),
+// which differ in the rows they take and nothing else.
 static cs336::SkinnyParams skinny_params(const char* op, const char* wn, cs336::SkinnyFormat f, const at::Tensor& x,
-                                         const at::Tensor& w, at::Tensor& out, bool wq = false) {
+                                         const at::Tensor& w, at::Tensor& out, int wq = 0) {
   const int64_t kl = cs336::skinny_k_per_load(f);
   const int64_t kpw = f == cs336::SkinnyFormat::MXFP4 ? 2 : 1, wl = kl / kpw;
   check_cuda(x, "x");
@@ -2216,10 +2218,12 @@ static cs336::SkinnyParams skinny_params(const char* op, const char* wn, cs336::
   TORCH_CHECK(w.device() == x.device() && out.device() == x.device(), "cs336: ", op, " tensors must be on one device");
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) * kpw == K && out.size(0) == M && out.size(1) == N, "cs336: ", op, " shape mismatch");
-  const int64_t m_lo = wq ? cs336::kWqMinM : 1, m_hi = wq ? cs336::kWqMaxM : 16;
+  const int64_t m_lo = wq == 2 ? cs336::kWqtMinM : (wq ? cs336::kWqMinM : 1);
+  const int64_t m_hi = wq == 2 ? ((int64_t)1 << 24) - 1 : (wq ? cs336::kWqMaxM : 16);
   TORCH_CHECK(M >= m_lo && M <= m_hi, "cs336: ", op, " takes ", m_lo, " <= M <= ", m_hi, " (got ", M, ")");
   TORCH_CHECK(K >= kl && K % kl == 0, "cs336: ", op, " needs K % ", kl, " == 0 (got ", K, ")");
-  TORCH_CHECK(wq ? cs336::gemm_wq_ok(f, M, N, K, x.element_size()) : cs336::gemm_skinny_ok(f, M, N, K, x.element_size()), "cs336: ", op,
+  TORCH_CHECK(wq == 2 ? cs336::gemm_wqt_ok(f, M, N, K, x.element_size())
+                      : (wq ? cs336::gemm_wq_ok(f, M, N, K, x.element_size()) : cs336::gemm_skinny_ok(f, M, N, K, x.element_size())), "cs336: ", op,
               " extents exceed the kernel's 32-bit row / k indices");
   TORCH_CHECK(x.stride(1) == 1 && w.stride(1) == 1 && out.stride(1) == 1, "cs336: ", op, " operands must have a contiguous last dim");
   TORCH_CHECK(x.stride(0) % 8 == 0 && (M == 1 || x.stride(0) >= 0), "cs336: ", op, " x row stride must be a non-negative multiple of 8");
@@ -2249,7 +2253,20 @@ void gemm_skinny(const at::Tensor& x, const at::Tensor& w, at::Tensor& out) {
   cs336::gemm_skinny(p, cs336::SkinnyFormat::W16, to_dtype(x), stream());
 }
 
-static void w8_op(const char* op, bool wide, const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
+// The launch of row class `wide` (skinny_params' wq). The tile GEMM's split-K plans take an fp32 workspace
+// from the caching allocator: stream-ordered, and part of a captured graph's pool under capture.
+static void wide_launch(int wide, const cs336::SkinnyParams& p, cs336::SkinnyFormat f, const at::Tensor& x) {
+  if (wide == 2) {
+    const int64_t n = cs336::wqt_workspace_floats(f, p.M, p.N, p.K);
+    at::Tensor ws;
+    if (n) ws = at::empty({n}, x.options().dtype(at::kFloat));
+    cs336::gemm_wqt(p, n ? ws.data_ptr<float>() : nullptr, f, to_dtype(x), stream());
+  } else {
+    (wide ? cs336::gemm_wq : cs336::gemm_skinny)(p, f, to_dtype(x), stream());
+  }
+}
+
+static void w8_op(const char* op, int wide, const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
   check_cuda(scale, "scale");
   TORCH_CHECK(scale.dim() == 1, "cs336: ", op, " takes x (M, K), wq (N, K), scale (N,), out (M, N)");
   TORCH_CHECK(wq.scalar_type() == at::kFloat8_e4m3fn || wq.scalar_type() == at::kByte,
@@ -2260,10 +2277,10 @@ static void w8_op(const char* op, bool wide, const at::Tensor& x, const at::Tens
   TORCH_CHECK(scale.size(0) == p.N && scale.is_contiguous(), "cs336: ", op, " scale must be contiguous with N = ", p.N, " elements");
   p.scale = scale.data_ptr<float>();
   c10::DeviceGuard g(x.device());
-  (wide ? cs336::gemm_wq : cs336::gemm_skinny)(p, cs336::SkinnyFormat::E4M3, to_dtype(x), stream());
+  wide_launch(wide, p, cs336::SkinnyFormat::E4M3, x);
 }
 
-static void w4_op(const char* op, bool wide, const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
+static void w4_op(const char* op, int wide, const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
   check_cuda(scale, "scale");
   TORCH_CHECK(scale.dim() == 2, "cs336: ", op, " takes x (M, K), wq (N, K/2), scale (N, K/32), out (M, N)");
   TORCH_CHECK(wq.scalar_type() == at::kByte || wq.scalar_type() == at::ScalarType::Float4_e2m1fn_x2, "cs336: ", op, " takes wq as uint8 or float4_e2m1fn_x2");
@@ -2276,23 +2293,23 @@ static void w4_op(const char* op, bool wide, const at::Tensor& x, const at::Tens
   p.bscale = static_cast<const uint8_t*>(scale.data_ptr());
   p.ldbs = p.N == 1 ? 0 : scale.stride(0);
   c10::DeviceGuard g(x.device());
-  (wide ? cs336::gemm_wq : cs336::gemm_skinny)(p, cs336::SkinnyFormat::MXFP4, to_dtype(x), stream());
+  wide_launch(wide, p, cs336::SkinnyFormat::MXFP4, x);
 }
 
 void gemm_skinny_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
-  w8_op("gemm_skinny_w8", false, x, wq, scale, out);
+  w8_op("gemm_skinny_w8", 0, x, wq, scale, out);
 }
 void gemm_skinny_w4(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
-  w4_op("gemm_skinny_w4", false, x, wq, scale, out);
+  w4_op("gemm_skinny_w4", 0, x, wq, scale, out);
 }
 
 // The same two products for 17 <= M <= 128 rows (csrc/gemm/gemm_wq.hip): operands and checks as above.
 // gemm_wq_plan: the (RW, KG, TN) the launch for (M, N, K) uses; w4: the MXFP4 format, else e4m3.
 void gemm_wq_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
-  w8_op("gemm_wq_w8", true, x, wq, scale, out);
+  w8_op("gemm_wq_w8", 1, x, wq, scale, out);
 }
 void gemm_wq_w4(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
-  w4_op("gemm_wq_w4", true, x, wq, scale, out);
+  w4_op("gemm_wq_w4", 1, x, wq, scale, out);
 }
 bool gemm_wq_w8_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
   return cs336::gemm_wq_ok(cs336::SkinnyFormat::E4M3, M, N, K, elem_size);
@@ -2306,6 +2323,27 @@ std::vector<int64_t> gemm_wq_plan(bool w4, int64_t M, int64_t N, int64_t K) {
   int rw, kg, tn;
   cs336::gemm_wq_plan(f, (int)M, (int)N, (int)K, rw, kg, tn);
   return {rw, kg, tn};
+}
+
+// The same two products above 128 rows (csrc/gemm/gemm_wqt.hip): operands and checks as above.
+// gemm_wqt_plan: the (BM, BN, splits) the launch for (M, N, K) uses; w4: the MXFP4 format, else e4m3.
+void gemm_wqt_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
+  w8_op("gemm_wqt_w8", 2, x, wq, scale, out);
+}
+void gemm_wqt_w4(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale, at::Tensor& out) {
+  w4_op("gemm_wqt_w4", 2, x, wq, scale, out);
+}
+bool gemm_wqt_w8_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
+  return cs336::gemm_wqt_ok(cs336::SkinnyFormat::E4M3, M, N, K, elem_size);
+}
+bool gemm_wqt_w4_ok(int64_t M, int64_t N, int64_t K, int64_t elem_size) {
+  return cs336::gemm_wqt_ok(cs336::SkinnyFormat::MXFP4, M, N, K, elem_size);
+}
+std::vector<int64_t> gemm_wqt_plan(bool w4, int64_t M, int64_t N, int64_t K) {
+  const cs336::SkinnyFormat f = w4 ? cs336::SkinnyFormat::MXFP4 : cs336::SkinnyFormat::E4M3;
+  TORCH_CHECK(cs336::gemm_wqt_ok(f, M, N, K, 2), "cs336: gemm_wqt_plan takes shapes the kernel takes");
+  const cs336::WqtPlan p = cs336::gemm_wqt_plan(f, M, N, K);
+  return {p.bm, p.bn, p.split};
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2399,6 +2437,11 @@ TORCH_LIBRARY(cs336, m) {
   m.def("gemm_wq_w4(Tensor x, Tensor wq, Tensor scale, Tensor(a!) out) -> ()");
   m.def("gemm_wq_w4_ok(int M, int N, int K, int elem_size) -> bool", &gemm_wq_w4_ok);
   m.def("gemm_wq_plan(bool w4, int M, int N, int K) -> int[]", &gemm_wq_plan);
+  m.def("gemm_wqt_w8(Tensor x, Tensor wq, Tensor scale, Tensor(a!) out) -> ()");
+  m.def("gemm_wqt_w8_ok(int M, int N, int K, int elem_size) -> bool", &gemm_wqt_w8_ok);
+  m.def("gemm_wqt_w4(Tensor x, Tensor wq, Tensor scale, Tensor(a!) out) -> ()");
+  m.def("gemm_wqt_w4_ok(int M, int N, int K, int elem_size) -> bool", &gemm_wqt_w4_ok);
+  m.def("gemm_wqt_plan(bool w4, int M, int N, int K) -> int[]", &gemm_wqt_plan);
   m.def("gemm_skinny(Tensor x, Tensor w, Tensor(a!) out) -> ()");
   m.def("gemm_skinny_ok(int M, int N, int K, int elem_size) -> bool", &gemm_skinny_ok);
   m.def(
@@ -2520,6 +2563,8 @@ TORCH_LIBRARY_IMPL(cs336, CUDA, m) {
   m.impl("gemm_skinny_w4", &gemm_skinny_w4);
   m.impl("gemm_wq_w8", &gemm_wq_w8);
   m.impl("gemm_wq_w4", &gemm_wq_w4);
+  m.impl("gemm_wqt_w8", &gemm_wqt_w8);
+  m.impl("gemm_wqt_w4", &gemm_wqt_w4);
   m.impl("gemm_skinny", &gemm_skinny);
   m.impl("fa_decode", &fa_decode);
   m.impl("kv_append_rope", &kv_append_rope);

@@ -497,6 +497,13 @@ void gemm_skinny_w4(const SkinnyParams& p, DType t, hipStream_t s);  // the MXFP
 bool gemm_wq_ok(SkinnyFormat f, int64_t M, int64_t N, int64_t K, int64_t elem_size);
 void gemm_wq(const SkinnyParams& p, SkinnyFormat f, DType t, hipStream_t s);
 
+// ---- weight-only FP8 / MXFP4 tile GEMM for M > 128 (csrc/gemm/gemm_wqt.hip) ----
+// The same two products, SkinnyParams and operand rules for 129 rows and more: W converted once on its way
+// into LDS, 32x32x16 MFMA tiles, launch plan in csrc/gemm/gemm_wqt_plan.h. ws: fp32 workspace of
+// wqt_workspace_floats(f, M, N, K) elements, 16-B aligned, for the shapes whose plan splits K (else unused).
+bool gemm_wqt_ok(SkinnyFormat f, int64_t M, int64_t N, int64_t K, int64_t elem_size);
+void gemm_wqt(const SkinnyParams& p, float* ws, SkinnyFormat f, DType t, hipStream_t s);
+
 // ---- temperature / top-k sampler (csrc/ops/sample.hip) ----
 // One token per row of logits (B, V; bf16 / fp16 / fp32 (DType), contiguous last dim, any element-aligned
 // row stride >= 0, 1 <= V <= 2^30) from one caller-supplied uniform u in [0, 1) per row; the rule is in
